@@ -7,7 +7,18 @@ batch: reads xyz (24 B/pt), writes uv (16 B), status (1 B) and the 2N x 8
 column-major Jacobian (128 B) = 169 B/pt algorithmic traffic.
 
   python bench.py [--gpus N --steps K --warmup W] [--scaling weak|strong]
+                  [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line
+(metric, value, ms_per_step, the event-timed roofline fraction).
+--dump-outputs DIR then writes what the last timed step computed as
+DIR/{indices,uv,status,jacobian,uv_nonfinite,jacobian_nonfinite}.npy, finite
+numbers only (dump_outputs; `_rank<r>` is appended to the names at N > 1);
+the inputs are the same bits in every run.  --full adds everything
+measured beside the headline, each described below: the
+other scaling mode, the residual pass and its all-reduce, the BASELINE
+config-4/5 legs, the PMC traffic lookup and the CPU baselines.
 
 Launch: under a launcher (torchrun sets WORLD_SIZE) every process is one
 rank and --gpus must equal WORLD_SIZE (else exit 2).  Without one,
@@ -19,7 +30,7 @@ projects its own --points batch (disjoint seeded shards; total work grows
 with N).  --scaling strong: --points is the GLOBAL batch, split into
 contiguous shards (distributed.shard_range: 10M -> 1.25M per rank at 8 GPUs).
 The path is a pure per-point map, so the timed steps have no data-path
-collective; at N > 1 the line also carries the other scaling mode measured
+collective; with --full at N > 1 the line also carries the other scaling mode measured
 in the same run, and the north-star collective -- one RCCL all-reduce of
 (sum ||r||^2, n_valid) of a residual pass over each rank's shard -- timed on
 its own.  Timing is barrier + synchronize on both sides and the max over
@@ -76,6 +87,65 @@ def roofline_block(bytes_per_launch, input_bytes_per_launch, kernel_ms):
     return out
 
 
+DUMP_MAX_POINTS = 131_072  # x (8 + 4 + 24 + 24 * P) B per point = 31 MB for KB + J
+DUMP_SEED = 20251205
+
+
+def finite_parts(arr):
+    """(values, codes) of an f64 array for the dump, whose files hold finite
+    numbers only: values = arr with every non-finite element written as 0,
+    codes (f32) = 0 where arr is finite, 1 NaN, 2 +inf, 3 -inf -- together
+    they say exactly what arr held."""
+    import numpy as np
+    codes = np.zeros(arr.shape, dtype=np.float32)
+    codes[np.isnan(arr)] = 1
+    codes[np.isposinf(arr)] = 2
+    codes[np.isneginf(arr)] = 3
+    return np.where(codes == 0, arr, 0.0), codes
+
+
+def dump_outputs(dirpath, suffix, n, uv, st, jac):
+    """--dump-outputs: the arrays acm_project's caller holds after the last
+    timed step, as DIR/<name><suffix>.npy.  Batches over DUMP_MAX_POINTS are
+    sampled at a fixed seeded sorted subset of the points (`indices`, f64),
+    the same subset in every run: uv (m, 2) f64, status (m,) as f32,
+    jacobian (P, m, 2) f64.  Failed points hold NaN in uv, and some of them
+    in J: uv and jacobian are written as finite_parts' values, with the
+    codes beside them as uv_nonfinite / jacobian_nonfinite."""
+    import numpy as np
+    import torch
+    os.makedirs(dirpath, exist_ok=True)
+    if n > DUMP_MAX_POINTS:
+        rng = np.random.Generator(np.random.Philox(key=DUMP_SEED))
+        idx = np.sort(rng.choice(n, size=DUMP_MAX_POINTS, replace=False))
+    else:
+        idx = np.arange(n)
+    sel = torch.as_tensor(idx, dtype=torch.int64, device=uv.device)
+    arrays = {"indices": idx.astype(np.float64),
+              "status": st[sel].to(torch.float32).cpu().numpy()}
+    arrays["uv"], arrays["uv_nonfinite"] = finite_parts(uv[sel].cpu().numpy())
+    if jac is not None:
+        arrays["jacobian"], arrays["jacobian_nonfinite"] = finite_parts(
+            jac[:, sel].cpu().numpy())
+    for name, arr in arrays.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), arr)
+
+
+def seeded_points(n, **kw):
+    """samples.synthetic_points_device with torch's deterministic algorithms
+    on: its scatter of the edge points draws indices with replacement, and
+    which of two edge points lands on a repeated index is otherwise up to the
+    scatter kernel -- the inputs must be the same bits in every run."""
+    import torch
+    from apex_camera_models import samples
+    old = torch.are_deterministic_algorithms_enabled()
+    torch.use_deterministic_algorithms(True)
+    try:
+        return samples.synthetic_points_device(n, **kw)
+    finally:
+        torch.use_deterministic_algorithms(old)
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -100,7 +170,17 @@ def parse():
     ap.add_argument("--leg5-cells", type=int, default=100_000_000,
                     help="config 5: requested sample_points cells in total")
     ap.add_argument("--leg-steps", type=int, default=10)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: "
+                         "the other scaling mode (N > 1), the residual pass + all-reduce, the "
+                         "BASELINE legs (--legs), the PMC traffic lookup and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (uv, status, jacobian and "
+                         "the point indices they belong to) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def cpu_baseline(model_id, params, w, h, n, seconds, opt="O3"):
@@ -759,10 +839,9 @@ def main():
         """this rank's resident batch: (points tensor, n, global n)"""
         if mode == "weak":
             n = a.points
-            return samples.synthetic_points_device(n, offset=rank * n, layout=a.layout), n, \
-                n * world
+            return seeded_points(n, offset=rank * n, layout=a.layout), n, n * world
         lo, hi = shard_range(a.points, rank, world)
-        full = samples.synthetic_points_device(a.points, layout=a.layout)
+        full = seeded_points(a.points, layout=a.layout)
         if a.layout == "soa":
             pts = full[:, lo:hi].contiguous()
         else:
@@ -770,7 +849,7 @@ def main():
         del full
         return pts, hi - lo, a.points
 
-    def measure(mode):
+    def measure(mode, dump=None):
         pts, n, n_global = points(mode)
         uv = torch.empty((n, 2), dtype=torch.float64, device=dev)
         st = torch.empty((n,), dtype=torch.uint8, device=dev)
@@ -813,6 +892,8 @@ def main():
         out = {"value": round(n_global / (ms_per_step / 1e3) / 1e6, 2),
                "ms_per_step": round(ms_per_step, 5), "kernel_ms": round(kern_ms, 5),
                "points_per_rank": n, "global_points": n_global}
+        if dump:
+            dump_outputs(dump, f"_rank{rank}" if world > 1 else "", n, uv, st, jac)
         if a.verify_shards and mode == "strong":
             out["shards_match_single_projection"] = verify(pts, n, uv, st, jac)
         return out, (pts, n)
@@ -829,7 +910,7 @@ def main():
             gathered = [parts]
         if rank != 0:
             return True
-        full = samples.synthetic_points_device(a.points, layout=a.layout)
+        full = seeded_points(a.points, layout=a.layout)
         N = a.points
         uv1 = torch.empty((N, 2), dtype=torch.float64, device=dev)
         st1 = torch.empty((N,), dtype=torch.uint8, device=dev)
@@ -847,9 +928,9 @@ def main():
         return bool(ok)
 
     wd.arm(f"{a.scaling}-scaling timed steps")
-    main_res, (pts, n) = measure(a.scaling)
+    main_res, (pts, n) = measure(a.scaling, a.dump_outputs)
     other = None
-    if world > 1:  # the other scaling mode, same process group, same run
+    if a.full and world > 1:  # the other scaling mode, same process group, same run
         del pts
         other_mode = "strong" if a.scaling == "weak" else "weak"
         wd.arm(f"{other_mode}-scaling timed steps")
@@ -857,67 +938,70 @@ def main():
         other["mode"] = other_mode
         pts, n, _ = points(a.scaling)  # the residual pass below runs on the primary shard
 
-    wd.arm("residual pass + all-reduce")
-    # The north-star collective: per rank one residual pass over its shard
-    # (acm_reprojection_stats against observations projected with fx * 1.01),
-    # then ONE all-reduce of (sum ||r||^2, n_valid) -- timed on its own.
-    pcam = _lib.AcmCamera()
-    pparams = list(params)
-    pparams[0] *= 1.01
-    _lib.check(L.acm_camera_init(ctypes.byref(pcam), model_id,
-                                 (ctypes.c_double * P)(*pparams), P, w, h))
-    obs = torch.empty((n, 2), dtype=torch.float64, device=dev)
-    sto = torch.empty((n,), dtype=torch.uint8, device=dev)
-    pts_aos = pts if a.layout == "aos" else pts.t().contiguous()
-    _lib.check(L.acm_project(ctypes.byref(pcam), n, pts_aos.data_ptr(), _lib.LAYOUT_AOS,
-                             obs.data_ptr(), sto.data_ptr(), None, sh))
-    res = torch.empty((8,), dtype=torch.float64, device=dev)
-    ws_b = L.acm_reprojection_stats_workspace_size(n)
-    ws = torch.empty(((ws_b + 7) // 8,), dtype=torch.float64, device=dev)
-    _lib.check(L.acm_reprojection_stats(ctypes.byref(cam), n, pts_aos.data_ptr(),
-                                        _lib.LAYOUT_AOS, obs.data_ptr(), res.data_ptr(), None,
-                                        ws.data_ptr(), ws_b, sh))
-    vec = torch.stack([res[7], res[5]]).to(cdev).contiguous()  # (sum ||r||^2, n_valid)
-    coll = {"op": "all_reduce(sum) of [sum ||r||^2, n_valid] (16 B)", "ranks": world}
-    if world > 1:
-        red = vec.clone()
-        for _ in range(3):
-            red.copy_(vec)
-            dist.all_reduce(red)
-        torch.cuda.synchronize()
-        reps = 20
-        dist.barrier()
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            red.copy_(vec)
-            dist.all_reduce(red)
-        torch.cuda.synchronize()
-        us = (time.perf_counter() - t0) / reps * 1e6
-        t = torch.tensor([us], dtype=torch.float64, device=cdev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        coll["us"] = round(float(t[0]), 2)
-        coll["backend"] = dist.get_backend()
-    else:
-        red = vec
-        coll["us"] = None
-        coll["backend"] = None
-    red = red.cpu()
-    coll["global_sum_sq_px2"] = float(red[0])
-    coll["global_n_valid"] = int(red[1])
-    coll["global_rmse_px"] = (float(red[0]) / float(red[1])) ** 0.5 if float(red[1]) else None
+    # Everything beside the headline runs only with --full: a plain run ends
+    # with its timed steps (and --dump-outputs) and prints the line.
+    coll, legs = None, {}
+    if a.full:
+        wd.arm("residual pass + all-reduce")
+        # The north-star collective: per rank one residual pass over its shard
+        # (acm_reprojection_stats against observations projected with fx * 1.01),
+        # then ONE all-reduce of (sum ||r||^2, n_valid) -- timed on its own.
+        pcam = _lib.AcmCamera()
+        pparams = list(params)
+        pparams[0] *= 1.01
+        _lib.check(L.acm_camera_init(ctypes.byref(pcam), model_id,
+                                     (ctypes.c_double * P)(*pparams), P, w, h))
+        obs = torch.empty((n, 2), dtype=torch.float64, device=dev)
+        sto = torch.empty((n,), dtype=torch.uint8, device=dev)
+        pts_aos = pts if a.layout == "aos" else pts.t().contiguous()
+        _lib.check(L.acm_project(ctypes.byref(pcam), n, pts_aos.data_ptr(), _lib.LAYOUT_AOS,
+                                 obs.data_ptr(), sto.data_ptr(), None, sh))
+        res = torch.empty((8,), dtype=torch.float64, device=dev)
+        ws_b = L.acm_reprojection_stats_workspace_size(n)
+        ws = torch.empty(((ws_b + 7) // 8,), dtype=torch.float64, device=dev)
+        _lib.check(L.acm_reprojection_stats(ctypes.byref(cam), n, pts_aos.data_ptr(),
+                                            _lib.LAYOUT_AOS, obs.data_ptr(), res.data_ptr(), None,
+                                            ws.data_ptr(), ws_b, sh))
+        vec = torch.stack([res[7], res[5]]).to(cdev).contiguous()  # (sum ||r||^2, n_valid)
+        coll = {"op": "all_reduce(sum) of [sum ||r||^2, n_valid] (16 B)", "ranks": world}
+        if world > 1:
+            red = vec.clone()
+            for _ in range(3):
+                red.copy_(vec)
+                dist.all_reduce(red)
+            torch.cuda.synchronize()
+            reps = 20
+            dist.barrier()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                red.copy_(vec)
+                dist.all_reduce(red)
+            torch.cuda.synchronize()
+            us = (time.perf_counter() - t0) / reps * 1e6
+            t = torch.tensor([us], dtype=torch.float64, device=cdev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            coll["us"] = round(float(t[0]), 2)
+            coll["backend"] = dist.get_backend()
+        else:
+            red = vec
+            coll["us"] = None
+            coll["backend"] = None
+        red = red.cpu()
+        coll["global_sum_sq_px2"] = float(red[0])
+        coll["global_n_valid"] = int(red[1])
+        coll["global_rmse_px"] = (float(red[0]) / float(red[1])) ** 0.5 if float(red[1]) else None
 
-    # BASELINE configs 4 and 5 (the multi-GPU configs), after the headline's
-    # timed region and its collective: sub-objects of the one line
-    want_legs = set() if a.legs == "none" else set(a.legs.split(","))
-    legs = {}
-    if want_legs:
-        del pts, obs, sto, pts_aos
-        torch.cuda.empty_cache()
-        ctx = LegCtx(rank, world, dist if world > 1 else None, cdev)
-        legs = run_legs(want_legs, [("4", "config4",
-                                     lambda: leg_config4(ctx, a.leg4_points, a.leg_steps)),
-                                    ("5", "config5", lambda: leg_config5(ctx, a.leg5_cells))], wd)
-        torch.cuda.empty_cache()
+        # BASELINE configs 4 and 5 (the multi-GPU configs), after the headline's
+        # timed region and its collective: sub-objects of the one line
+        want_legs = set() if a.legs == "none" else set(a.legs.split(","))
+        if want_legs:
+            del pts, obs, sto, pts_aos
+            torch.cuda.empty_cache()
+            ctx = LegCtx(rank, world, dist if world > 1 else None, cdev)
+            legs = run_legs(want_legs, [
+                ("4", "config4", lambda: leg_config4(ctx, a.leg4_points, a.leg_steps)),
+                ("5", "config5", lambda: leg_config5(ctx, a.leg5_cells))], wd)
+            torch.cuda.empty_cache()
 
     if rank == 0:
         bpp = 24 + 16 + 1 + (16 * P if want_j else 0)
@@ -925,7 +1009,9 @@ def main():
         achieved = bpp * main_res["points_per_rank"] / (kern_ms / 1e3) / 1e9
         workload = (f"{a.model}_project{'_jacobian' if want_j else ''}_f64_"
                     f"{a.layout}")
-        traffic, traffic_src = load_traffic(workload, main_res["points_per_rank"])
+        traffic, traffic_src = None, "not looked up (--full)"
+        if a.full:
+            traffic, traffic_src = load_traffic(workload, main_res["points_per_rank"])
         out = {
             "metric": "Mpoints/sec project+Jacobian (KB, f64) at 1/2/4/8 GPU; % HBM roofline",
             "value": main_res["value"],
@@ -954,9 +1040,10 @@ def main():
                          "traffic": traffic, "traffic_source": traffic_src,
                          "algorithmic_bytes_per_launch": bpp * main_res["points_per_rank"],
                          "kernel_ms": kern_ms},
-            "collective": coll,
             "ranks_devices": ranks_devices,
         }
+        if coll is not None:
+            out["collective"] = coll
         if "shards_match_single_projection" in main_res:
             out["shards_match_single_projection"] = main_res["shards_match_single_projection"]
         if other is not None:
@@ -965,7 +1052,7 @@ def main():
             out[other["mode"]] = other
         out.update(legs)
         wd.arm("cpu baseline", 10 * tmo)
-        if not a.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
+        if a.full and not a.no_cpu_baseline and world == 1:  # rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(model_id, params, w, h, main_res["points_per_rank"],
                                                a.cpu_baseline_seconds)
             out["cpu_baseline_o2"] = cpu_baseline(model_id, params, w, h,

@@ -248,3 +248,47 @@ def test_failing_leg_keeps_the_headline():
     assert legs["config4"]["error"].startswith("MemoryError")
     assert legs["config5"] == {"value": 1.0}
     assert bench.run_legs(set(), [("4", "config4", boom)]) == {}
+
+
+def test_dump_outputs_sample_is_fixed_and_bounded(tmp_path):
+    """--dump-outputs: a batch over DUMP_MAX_POINTS is written at the same
+    sorted seeded subset of the points in every run, as finite f32 / f64
+    arrays of at most 64 MB in all at the headline's 8 + 2 parameters (what
+    was not finite is written as 0 and coded in <name>_nonfinite); a batch
+    under it is written whole"""
+    import numpy as np
+    import torch
+
+    import bench
+    n, P = bench.DUMP_MAX_POINTS + 1001, 8
+    g = torch.Generator().manual_seed(1)
+    uv = torch.rand((n, 2), dtype=torch.float64, generator=g)
+    st = (torch.arange(n) % 4).to(torch.uint8)
+    jac = torch.rand((P, n, 2), dtype=torch.float64, generator=g)
+    uv[::50] = float("nan")  # every 50th point, so the sample holds some
+    jac[:, ::100] = float("nan")
+    jac[2, 1::100, 1], jac[3, 1::100, 0] = float("inf"), float("-inf")
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "", n, uv, st, jac)
+    a = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(a) == ["indices", "jacobian", "jacobian_nonfinite", "status", "uv",
+                         "uv_nonfinite"]
+    for name, arr in a.items():
+        assert arr.dtype in (np.float32, np.float64) and np.isfinite(arr).all(), name
+        assert np.array_equal(arr, np.load(tmp_path / "b" / f"{name}.npy")), name
+    idx = a["indices"].astype(np.int64)
+    assert len(idx) == bench.DUMP_MAX_POINTS and (np.diff(idx) > 0).all() and idx[-1] < n
+    assert np.array_equal(a["status"], st.numpy()[idx].astype(np.float32))
+    # values + codes give back what the arrays held, NaN and infinities included
+    back = {1: np.nan, 2: np.inf, 3: -np.inf}
+    for name, full in (("uv", uv.numpy()[idx]), ("jacobian", jac.numpy()[:, idx])):
+        codes, vals = a[name + "_nonfinite"], a[name].copy()
+        assert (vals[codes != 0] == 0).all() and (codes != 0).sum() == (~np.isfinite(full)).sum()
+        for c, v in back.items():
+            vals[codes == c] = v
+        assert np.array_equal(vals, full, equal_nan=True), name
+    assert sum(arr.nbytes for arr in a.values()) <= 64_000_000
+    bench.dump_outputs(str(tmp_path / "c"), "_rank1", 100, uv[:100], st[:100], None)
+    assert sorted(os.listdir(tmp_path / "c")) == ["indices_rank1.npy", "status_rank1.npy",
+                                                  "uv_nonfinite_rank1.npy", "uv_rank1.npy"]
+    assert np.array_equal(np.load(tmp_path / "c" / "indices_rank1.npy"), np.arange(100.0))

@@ -9,7 +9,7 @@
 # Steps:
 #   tests[=ARGS]       pytest -m gpu over tests/ (or ARGS: files / -k expr)
 #   smoke              __graft_entry__.smoke()
-#   bench              python bench.py (the driver's default line)
+#   bench              python bench.py --full (the headline and everything beside it)
 #   prof               rocprofv3 kernel trace of bench.py (no CPU baseline)
 #   pmc                headline PMC passes (FETCH/WRITE_SIZE, EA requests)
 #                      + profiles/collect_pmc.py summary
@@ -56,7 +56,7 @@ for step in "$@"; do
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/${TAG}_smoke.log 2>&1
     check $? smoke; tail -n 1 $O/${TAG}_smoke.log ;;
   bench)
-    timeout -k 10 300 python bench.py > $O/${TAG}_bench.log 2>&1
+    timeout -k 10 300 python bench.py --full > $O/${TAG}_bench.log 2>&1
     check $? bench; tail -c 700 $O/${TAG}_bench.log; echo ;;
   prof)
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_prof -o kt \
