@@ -13,9 +13,12 @@ from . import camera, factors, util  # noqa: E402
 from .camera import (CameraModel, CameraModelError, DoubleSphereModel, EucmModel,  # noqa: E402
                      FovModel, Intrinsics, KannalaBrandtModel, PinholeModel, RadTanModel,
                      Resolution, UcmModel)
+from .util import (ImageQualityMetrics, calculate_psnr, calculate_ssim,  # noqa: E402
+                   compute_image_quality_metrics)
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
     "EucmModel", "FovModel", "Intrinsics", "KannalaBrandtModel", "PinholeModel", "RadTanModel",
-    "Resolution", "UcmModel",
+    "Resolution", "UcmModel", "ImageQualityMetrics", "calculate_psnr", "calculate_ssim",
+    "compute_image_quality_metrics",
 ]

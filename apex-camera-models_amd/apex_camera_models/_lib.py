@@ -26,6 +26,8 @@ PINHOLE, RADTAN, KANNALA_BRANDT, DOUBLE_SPHERE, UCM, EUCM, FOV = range(7)
 LAYOUT_AOS, LAYOUT_SOA = 0, 1
 EXACT_MATH = 0x100  # OR-ed into acm_project's layout (include/acm.h)
 REFERENCE_NEWTON = 0x200  # OR-ed into acm_unproject's layout / acm_sample_points_ex's flags
+RASTER_ACCUMULATE = 1  # acm_projection_masks / acm_raster_points flags
+RASTER_EXACT_ALL = 2  # acm_projection_masks: no guard band, every point projected exactly
 INVALID_SKIP, INVALID_SENTINEL = 0, 1
 MAX_PARAMS = 9
 
@@ -180,6 +182,13 @@ EXPORTED_SYMBOLS = (
     "acm_sample_points_ray_poly",
     "acm_sample_points_ray_fit",
     "acm_undistort_image",
+    "acm_projection_masks_workspace_size",
+    "acm_projection_masks",
+    "acm_raster_points",
+    "acm_compose_projection_image",
+    "acm_image_quality_workspace_size",
+    "acm_image_quality",
+    "acm_image_quality_finish",
     "acm_set_device",
     "acm_device_malloc",
     "acm_device_free",
@@ -349,6 +358,23 @@ def load():
     L.acm_median_valid_allreduce.restype = i
     L.acm_undistort_image.argtypes = [cam_p, ctypes.POINTER(ctypes.c_double), i, vp, vp, vp]
     L.acm_undistort_image.restype = i
+    u32 = ctypes.c_uint32
+    rgb_p = ctypes.POINTER(ctypes.c_uint8)
+    L.acm_projection_masks_workspace_size.argtypes = [u32, u32]
+    L.acm_projection_masks_workspace_size.restype = sz
+    L.acm_projection_masks.argtypes = [cam_p, cam_p, u32, u32, sz, vp, i, i, vp, vp, vp, vp, sz, vp]
+    L.acm_projection_masks.restype = i
+    L.acm_raster_points.argtypes = [u32, u32, sz, vp, i, vp, vp, sz, vp]
+    L.acm_raster_points.restype = i
+    L.acm_compose_projection_image.argtypes = [u32, u32, vp, vp, rgb_p, rgb_p, vp, vp, vp]
+    L.acm_compose_projection_image.restype = i
+    L.acm_image_quality_workspace_size.argtypes = [u32, u32]
+    L.acm_image_quality_workspace_size.restype = sz
+    L.acm_image_quality.argtypes = [u32, u32, vp, vp, vp, vp, vp, sz, vp]
+    L.acm_image_quality.restype = i
+    L.acm_image_quality_finish.argtypes = [vp, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.POINTER(ctypes.c_double)]
+    L.acm_image_quality_finish.restype = i
     L.acm_set_device.argtypes = [i]
     L.acm_set_device.restype = i
     L.acm_device_malloc.argtypes = [ctypes.POINTER(vp), sz]

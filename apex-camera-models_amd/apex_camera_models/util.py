@@ -2,7 +2,10 @@
 
 `sample_points` (point_sampling.rs:46-120) and `compute_reprojection_error`
 (error_metrics.rs:62-121), both evaluated by libacm.so kernels on device
-tensors.
+tensors; `undistort_image` (undistort.rs), `validate_conversion_accuracy`
+(validation.rs) and the projection rasters, overlay picture and PSNR / SSIM
+of image_quality.rs (below: the fused dual-projection raster kernel, PNG
+output with the standard library only).
 """
 from __future__ import annotations
 
@@ -382,3 +385,309 @@ def validate_conversion_accuracy(output_model: CameraModel,
         status = "NEEDS IMPROVEMENT"
     return ValidationResults(*errs, average_error=avg, max_error=max_error, status=status,
                              region_data=data)
+
+
+# ------------------------------------------------------------- image quality
+# Mirror of src/util/image_quality.rs.  Images are (H, W, 3) uint8 device
+# tensors (RGB8, row-major); a projection raster is a set of pixels (every
+# disc of one raster has one colour), built as a (H, W) uint8 0 / 1 mask.
+GREEN, MAGENTA, WHITE = (0, 255, 0), (255, 0, 255), (255, 255, 255)
+
+
+@dataclass
+class ImageQualityMetrics:
+    """image_quality.rs:14-24, plus the overlay picture the reference only
+    writes to disk and the number of points that passed the filter."""
+    psnr: float
+    ssim: float
+    overlay: object = None  # (H, W, 3) uint8 device tensor
+    n_kept: int = 0
+
+
+def _as_rgb8(image) -> torch.Tensor:
+    img = image if isinstance(image, torch.Tensor) else torch.as_tensor(image)
+    if img.dim() != 3 or img.shape[2] != 3 or img.shape[0] == 0 or img.shape[1] == 0:
+        raise UtilError("expected a non-empty (H, W, 3) RGB8 image")
+    return img.to("cuda", torch.uint8).contiguous()
+
+
+def _rgb(color):
+    c = [int(v) for v in color]
+    if len(c) != 3 or any(v < 0 or v > 255 for v in c):
+        raise UtilError("a colour is three bytes (r, g, b)")
+    return (ctypes.c_uint8 * 3)(*c)
+
+
+def _image_size(width, height):
+    w, h = int(width), int(height)
+    if w <= 0 or h <= 0:
+        raise UtilError("width and height must be positive")
+    return w, h
+
+
+def image_quality_sums(img1, img2, ssim_map: bool = False):
+    """acm_image_quality's raw result: (sse, valid, ssim_sum, ssim_count,
+    per-pixel SSIM map or None) -- the two integer sums of PSNR, the sum and
+    the number of the SSIM terms (include/acm.h)."""
+    import struct
+    L = _lib.load()
+    a, b = _as_rgb8(img1), _as_rgb8(img2)
+    if a.shape != b.shape:  # :46-50, :109-113
+        raise UtilError("Images must have the same dimensions")
+    h, w = a.shape[0], a.shape[1]
+    res = torch.empty((4,), dtype=torch.int64, device=a.device)
+    smap = None
+    if ssim_map:
+        smap = torch.empty((max(h - 2, 0), max(w - 2, 0)), dtype=torch.float64, device=a.device)
+    ws_bytes = L.acm_image_quality_workspace_size(w, h)
+    ws = _workspace(ws_bytes, a.device)
+    _lib.check(L.acm_image_quality(w, h, a.data_ptr(), b.data_ptr(), res.data_ptr(),
+                                   smap.data_ptr() if smap is not None and smap.numel() else None,
+                                   ws.data_ptr(), ws_bytes, _stream_handle()))
+    sse, valid, ssim_sum, count = struct.unpack("<QQdQ", struct.pack("<4q", *res.cpu().tolist()))
+    return sse, valid, ssim_sum, count, smap
+
+
+def image_quality(img1, img2):
+    """(psnr, ssim) of two images: one acm_image_quality launch, one 32-B
+    read, the reference's closing arithmetic on the host
+    (acm_image_quality_finish)."""
+    import struct
+    sse, valid, ssim_sum, count, _ = image_quality_sums(img1, img2)
+    psnr, ssim = ctypes.c_double(), ctypes.c_double()
+    _lib.check(_lib.load().acm_image_quality_finish(
+        struct.pack("<QQdQ", sse, valid, ssim_sum, count), ctypes.byref(psnr),
+        ctypes.byref(ssim)))
+    return psnr.value, ssim.value
+
+
+def calculate_psnr(img1, img2) -> float:
+    """`calculate_psnr` (:45-89): dB, +inf for a perfect match; pixel pairs
+    that are black in both images are skipped."""
+    return image_quality(img1, img2)[0]
+
+
+def calculate_ssim(img1, img2) -> float:
+    """`calculate_ssim` (:108-210): mean 3 x 3-window SSIM of the gray images
+    over the interior pixels, 1.0 when there are none."""
+    return image_quality(img1, img2)[1]
+
+
+def raster_points(projections, width: int, height: int, out=None) -> torch.Tensor:
+    """The (H, W) uint8 mask of radius-2 discs around `projections` (N, 2)
+    (:353-369).  out: an existing mask to OR into (ACM_RASTER_ACCUMULATE)."""
+    L = _lib.load()
+    w, h = _image_size(width, height)
+    p2 = _as_device_f64(projections, 2)
+    n = p2.shape[0]
+    mask = out if out is not None else torch.empty((h, w), dtype=torch.uint8, device=p2.device)
+    ws_bytes = L.acm_projection_masks_workspace_size(w, h)
+    ws = _workspace(ws_bytes, p2.device)
+    _lib.check(L.acm_raster_points(w, h, n, p2.data_ptr() if n else None,
+                                   _lib.RASTER_ACCUMULATE if out is not None else 0,
+                                   mask.data_ptr(), ws.data_ptr(), ws_bytes, _stream_handle()))
+    return mask
+
+
+def projection_masks(input_model: CameraModel, output_model: CameraModel, points_3d,
+                     width: int, height: int, layout: str = "aos", out=None,
+                     exact_all: bool = False):
+    """The fused per-point pass of compute_image_quality_metrics (:272-293 and
+    the two comparison rasters, :314-317): (input_mask, output_mask, n_kept)
+    -- two (H, W) uint8 device masks and a one-element int64 device tensor.
+    layout "soa": points_3d is (3, N).  out: the triple of an earlier call to
+    accumulate into (another chunk of the same point set).  exact_all:
+    ACM_RASTER_EXACT_ALL (every point projected exactly instead of only those
+    in the guard band of a decision; the same masks)."""
+    L = _lib.load()
+    w, h = _image_size(width, height)
+    if layout == "soa":
+        p3 = points_3d if isinstance(points_3d, torch.Tensor) else torch.as_tensor(points_3d)
+        p3 = p3.to("cuda", torch.float64).reshape(3, -1).contiguous()
+        n = p3.shape[1]
+    else:
+        p3 = _as_device_f64(points_3d, 3)
+        n = p3.shape[0]
+    if out is not None:
+        m_in, m_out, kept = out
+    else:
+        m_in = torch.empty((h, w), dtype=torch.uint8, device=p3.device)
+        m_out = torch.empty((h, w), dtype=torch.uint8, device=p3.device)
+        kept = torch.empty((1,), dtype=torch.int64, device=p3.device)
+    ws_bytes = L.acm_projection_masks_workspace_size(w, h)
+    ws = _workspace(ws_bytes, p3.device)
+    ci, co = input_model.acm_camera(), output_model.acm_camera()
+    _lib.check(L.acm_projection_masks(
+        ctypes.byref(ci), ctypes.byref(co), w, h, n, p3.data_ptr() if n else None,
+        _lib.LAYOUT_SOA if layout == "soa" else _lib.LAYOUT_AOS,
+        (_lib.RASTER_ACCUMULATE if out is not None else 0) |
+        (_lib.RASTER_EXACT_ALL if exact_all else 0), m_in.data_ptr(), m_out.data_ptr(),
+        kept.data_ptr(), ws.data_ptr(), ws_bytes, _stream_handle()))
+    return m_in, m_out, kept
+
+
+def compose_projection_image(width: int, height: int, input_mask=None, output_mask=None,
+                             input_color=GREEN, output_color=MAGENTA,
+                             background=None) -> torch.Tensor:
+    """output_color where output_mask is set, else input_color where
+    input_mask is set, else the background (None: black) -- the result of
+    drawing all input discs and then all output discs (:388-510)."""
+    w, h = _image_size(width, height)
+    bg = None
+    if background is not None:
+        bg = _as_rgb8(background)
+        if bg.shape[0] != h or bg.shape[1] != w:
+            raise UtilError("the background must be (height, width, 3)")
+    img = torch.empty((h, w, 3), dtype=torch.uint8, device="cuda")
+    _lib.check(_lib.load().acm_compose_projection_image(
+        w, h, input_mask.data_ptr() if input_mask is not None else None,
+        output_mask.data_ptr() if output_mask is not None else None, _rgb(input_color),
+        _rgb(output_color), bg.data_ptr() if bg is not None else None, img.data_ptr(),
+        _stream_handle()))
+    return img
+
+
+def create_projection_image(projections, color, width: int, height: int) -> torch.Tensor:
+    """`create_projection_image` (:338-373): discs of ONE colour on black.
+    The reference takes a colour per point; every caller passes a uniform
+    list, and per-point colours would make the picture depend on the order
+    of the points, so this takes the one colour."""
+    mask = raster_points(projections, width, height)
+    return compose_projection_image(width, height, input_mask=mask, input_color=color)
+
+
+def create_combined_projection_image(input_projections, output_projections, width: int,
+                                     height: int) -> torch.Tensor:
+    """`create_combined_projection_image` (:454-510): input discs green,
+    then output discs magenta, on black."""
+    return compose_projection_image(width, height,
+                                    raster_points(input_projections, width, height),
+                                    raster_points(output_projections, width, height))
+
+
+def create_combined_projection_image_on_reference(input_projections, output_projections,
+                                                  reference_image) -> torch.Tensor:
+    """`create_combined_projection_image_on_reference` (:388-438): the same
+    on a copy of the reference image."""
+    ref = _as_rgb8(reference_image)
+    h, w = ref.shape[0], ref.shape[1]
+    return compose_projection_image(w, h, raster_points(input_projections, w, h),
+                                    raster_points(output_projections, w, h), background=ref)
+
+
+def _png_bytes(image) -> bytes:
+    """8-bit RGB PNG of an (H, W, 3) uint8 array: filter type 0 on every row,
+    one zlib stream (standard library only)."""
+    import struct
+    import zlib
+    img = image.cpu().numpy() if isinstance(image, torch.Tensor) else image
+    if img.ndim != 3 or img.shape[2] != 3 or str(img.dtype) != "uint8":
+        raise UtilError("expected an (H, W, 3) uint8 image")
+    h, w = int(img.shape[0]), int(img.shape[1])
+    raw = b"".join(b"\x00" + img[y].tobytes() for y in range(h))
+
+    def chunk(tag, data):
+        return (struct.pack(">I", len(data)) + tag + data +
+                struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF))
+    return (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) +
+            chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+def write_png(path: str, image) -> None:
+    with open(path, "wb") as f:
+        f.write(_png_bytes(image))
+
+
+def save_model_projection_image(image, model_name: str, output_dir: str = "output") -> str:
+    """`save_model_projection_image` (:526-539): writes
+    <output_dir>/<lowercased name, spaces as underscores>_projection.png and
+    returns the path (the reference always writes under output/)."""
+    import os
+    try:
+        os.makedirs(output_dir, exist_ok=True)
+        path = os.path.join(output_dir,
+                            model_name.lower().replace(" ", "_") + "_projection.png")
+        write_png(path, image)
+    except OSError as e:
+        raise UtilError(f"Failed to save projection image: {e}") from e
+    return path
+
+
+def load_image(image_path: str) -> torch.Tensor:
+    """`load_image` (:225-230): the file as an (H, W, 3) uint8 host tensor.
+    Decoding uses Pillow when it is importable; UtilError otherwise."""
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise UtilError("load_image needs Pillow to decode image files") from e
+    import numpy as np
+    try:
+        with Image.open(image_path) as im:
+            arr = np.array(im.convert("RGB"), dtype=np.uint8)
+    except Exception as e:  # noqa: BLE001  (:226-227: any failure is InvalidParams)
+        raise UtilError(f"Failed to load image: {e}") from e
+    return torch.from_numpy(arr)
+
+
+def compute_image_quality_metrics(input_model: CameraModel, output_model: CameraModel,
+                                  points_3d, output_model_name: str = None,
+                                  reference_image=None,
+                                  output_dir: str = None) -> ImageQualityMetrics:
+    """`compute_image_quality_metrics` (:252-324).  The optimisation points go
+    through both models in one fused kernel (acm_projection_masks) that keeps
+    a point iff both projections are Ok and the output pixel lies in the
+    image -- the reference image's size when one is given, else the input
+    model's resolution -- and rasterises both pixel sets; PSNR / SSIM compare
+    the two white-on-black rasters, and the overlay (input green, output
+    magenta, on the reference image or black) is returned in the result.
+
+    The reference always writes the overlay to output/<name>_projection.png;
+    here a file is written only when output_dir is given (the name then
+    follows :530-531; output_model_name defaults to the model's own name).
+    Raises ZeroProjectionPoints when no point is kept (:295-297)."""
+    ref = None
+    if reference_image is not None:
+        ref = _as_rgb8(reference_image)
+        h, w = ref.shape[0], ref.shape[1]  # :260-261
+    else:
+        res = input_model.get_resolution()
+        w, h = _image_size(res.width, res.height)  # :263-264
+    m_in, m_out, kept = projection_masks(input_model, output_model, points_3d, w, h)
+    white_in = compose_projection_image(w, h, input_mask=m_in, input_color=WHITE)
+    white_out = compose_projection_image(w, h, input_mask=m_out, input_color=WHITE)
+    overlay = compose_projection_image(w, h, m_in, m_out, background=ref)
+    n_kept = int(kept.item())
+    if n_kept == 0:
+        raise ZeroProjectionPoints()
+    if output_dir is not None:
+        save_model_projection_image(overlay, output_model_name or output_model.get_model_name(),
+                                    output_dir)
+    psnr, ssim = image_quality(white_in, white_out)
+    return ImageQualityMetrics(psnr=psnr, ssim=ssim, overlay=overlay, n_kept=n_kept)
+
+
+def model_projection_visualization(points_2d, model_name: str, reference_image=None,
+                                   camera_resolution=None, output_dir: str = None) -> torch.Tensor:
+    """`model_projection_visualization` (:556-616): the pixels as green discs
+    on the reference image, or on black at camera_resolution = (width,
+    height).  Returns the picture; with output_dir it is also written to
+    <output_dir>/<lowercased name>_projection.png (:609; the reference always
+    writes under output/)."""
+    if reference_image is not None:
+        ref = _as_rgb8(reference_image)
+        h, w = ref.shape[0], ref.shape[1]
+        img = compose_projection_image(w, h, input_mask=raster_points(points_2d, w, h),
+                                       background=ref)
+    else:
+        if camera_resolution is None:
+            raise UtilError("camera_resolution is needed without a reference image")
+        w, h = camera_resolution
+        img = create_projection_image(points_2d, GREEN, w, h)
+    if output_dir is not None:
+        import os
+        try:
+            os.makedirs(output_dir, exist_ok=True)
+            write_png(os.path.join(output_dir, model_name.lower() + "_projection.png"), img)
+        except OSError as e:
+            raise UtilError(f"Failed to save projection image: {e}") from e
+    return img

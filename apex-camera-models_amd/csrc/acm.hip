@@ -3646,6 +3646,417 @@ __global__ __launch_bounds__(kBlock) void k_undistort(acm_camera cam, double tfx
     o[2] = b;
 }
 
+// ------------------------------------------------- projection rasters
+// util::compute_image_quality_metrics' per-point half (image_quality.rs
+// :272-293, :338-373): project every point through the input and the output
+// model, keep it iff both are Ok and the output pixel lies in the image, and
+// draw the two pixels as radius-2 discs.  All discs of one raster have one
+// colour, so the raster is a set of pixels: a bitmask (one bit per pixel,
+// rows padded to whole 32-bit words) filled with OR gives the reference's
+// image whatever the order of the points.
+//
+// Shape: a persistent grid strides over the points (24 B read per point, no
+// per-point output).  When the bitmasks fit kRasterLdsBudget every workgroup
+// keeps private copies in LDS, ORs its discs into them (an LDS atomic only
+// for words that still miss a bit: at ~355 points per pixel of the flagship
+// set almost every disc finds its bits set and costs 5 LDS reads), and at the
+// end ORs its non-zero words into the global bitmasks.  Larger images take
+// the same disc code on the global bitmasks: load the word, atomicOr only
+// the missing bits (a stale load only costs a redundant atomic).
+//
+// Both pixels are quantised by round(), so the decisions must be those of
+// the reference-exact projections (EXACT: IEEE sqrt / divisions, the
+// double-double atan2 for KB / FOV), as in k_undistort.  By default every
+// lane projects with the default math and only the lanes inside a guard band
+// of a decision are projected again exactly (k_projection_masks below).  The
+// two models are chosen by a wave-uniform switch on the camera's model id
+// (kernel arguments, SGPRs): one kernel holds the seven projections instead
+// of 49 kernels holding two.
+//
+// Workgroup: 1024 lanes.  The kernel needs 128 VGPRs, so a SIMD holds 4
+// waves and a CU 16: one workgroup fills a CU, beside 64 KiB (512 x 512) or
+// 92,160 B (752 x 480) of masks alike (resource usage in DESIGN 5.10).
+// kRasterLdsBudget = 96 KiB of the CU's 160: the flush (one pass over the
+// workgroup's LDS) grows with the image, so larger ones go to the global
+// path.
+constexpr int kRasterBlock = 1024;
+constexpr size_t kRasterLdsBudget = 96u << 10;
+constexpr int kRasterMaxBlocks = 2048;
+
+// OR `bits` into word *w unless they are all set already
+template <bool LDS>
+__device__ __forceinline__ void mask_or(uint32_t* w, uint32_t bits) {
+    if ((__atomic_load_n(w, __ATOMIC_RELAXED) & bits) != bits) atomicOr(w, bits);
+}
+
+// One disc (:353-369).  The centre is round() (half away from zero) then
+// Rust's `as i32` (NaN -> 0).  A centre outside [-2, W + 1] x [-2, H + 1]
+// has no pixel inside the image; that is decided on the f64 value, before
+// the cast, so centre + dx stays far from the integer range's ends (W, H <=
+// 2^30).  The disc is five row spans, 00100 / 01110 / 11111 / 01110 / 00100
+// from column cx - 2: the three patterns are shifted to that column's bit,
+// cut at the image's left and right edges once, and ORed into the one or two
+// words of each row that lies inside the image.
+template <bool LDS>
+__device__ __forceinline__ void draw_disc(uint32_t* mask, uint32_t wpr, int W, int H, double u,
+                                          double v) {
+    const double cu = round(u), cv = round(v);
+    if (cu < -2.0 || cu > (double)W + 1.0 || cv < -2.0 || cv > (double)H + 1.0) return;
+    const int cx = cu != cu ? 0 : (int)cu, cy = cv != cv ? 0 : (int)cv;
+    const int xs = cx - 2;              // the patterns' first column, >= -4
+    const int cut = xs < 0 ? -xs : 0;   // pattern columns left of the image
+    const uint32_t x0 = xs < 0 ? 0u : (uint32_t)xs;  // <= W - 1 (cx <= W + 1)
+    const uint32_t w0 = x0 >> 5, sh = x0 & 31u;
+    const uint32_t room = (uint32_t)W - (w0 << 5);  // image columns from word w0 on, >= 1
+    const uint64_t clip = room >= 64u ? ~0ull : (1ull << room) - 1ull;
+    const uint64_t m0 = ((uint64_t)(0x1fu >> cut) << sh) & clip;  // dy = 0
+    const uint64_t m1 = ((uint64_t)(0x0eu >> cut) << sh) & clip;  // |dy| = 1
+    const uint64_t m2 = ((uint64_t)(0x04u >> cut) << sh) & clip;  // |dy| = 2
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int y = cy + dy;
+        if (y < 0 || y >= H) continue;
+        const uint64_t m = dy == 0 ? m0 : (dy == 1 || dy == -1) ? m1 : m2;
+        const size_t row = LDS ? (size_t)((uint32_t)y * wpr) : (size_t)y * wpr;
+        uint32_t* w = mask + row + w0;
+        if ((uint32_t)m) mask_or<LDS>(w, (uint32_t)m);
+        // the upper half is non-zero only for columns < W: word w0 + 1 < wpr
+        if ((uint32_t)(m >> 32)) mask_or<LDS>(w + 1, (uint32_t)(m >> 32));
+    }
+}
+
+// EXACT: the reference-exact projection (camera_models.hpp), else the default
+// math.  The model is a kernel argument: a wave-uniform branch.
+template <bool EXACT>
+__device__ __forceinline__ uint8_t project_any(int model, const Cam<double>& c, double x,
+                                               double y, double z, double& u, double& v) {
+#define ACM_PX(M) M<double>::template project<false, false, EXACT>(c, x, y, z, u, v, nullptr, nullptr)
+    switch (model) {
+    case ACM_PINHOLE: return ACM_PX(Pinhole);
+    case ACM_RADTAN: return ACM_PX(RadTan);
+    case ACM_KANNALA_BRANDT: return ACM_PX(KannalaBrandt);
+    case ACM_DOUBLE_SPHERE: return ACM_PX(DoubleSphere);
+    case ACM_UCM: return ACM_PX(Ucm);
+    case ACM_EUCM: return ACM_PX(Eucm);
+    default: return ACM_PX(Fov);
+    }
+#undef ACM_PX
+}
+
+// Guard band of the default-math projection.  The default math is held to
+// |c - c_exact| <= 1e-10 max(|c_exact|, 1) per coordinate (camera_models.hpp,
+// tests/test_gpu_parity.py; statuses are bit-identical), and max(|c_exact|,
+// 1) <= (1 + 1e-10) max(|c|, 1) + 1e-10, so |c - c_exact| < band(c) = 2e-10
+// max(|c|, 1).  A coordinate farther than band(c) from every value at which
+// a decision changes -- k + 1/2 for round(), and 0 and the image size for
+// the output pixel's bounds test -- gives the decisions of c_exact.  c -
+// floor(c) and the differences below are exact for |c| < 2^52; larger or NaN
+// coordinates fail the tests (written so that NaN fails) and are recomputed.
+__device__ __forceinline__ bool off_half(double c) {
+    return fabs((c - floor(c)) - 0.5) > 2e-10 * fmax(fabs(c), 1.0);
+}
+__device__ __forceinline__ bool off_edge(double c, double size) {
+    const double band = 2e-10 * fmax(fabs(c), 1.0);
+    return fabs(c) > band && fabs(c - size) > band;
+}
+
+// words: 32-bit words of one bitmask (wpr * H); gmask: `nmasks` bitmasks of
+// `gstride` words each.  LDS: dynamic shared memory of nmasks * words words.
+template <bool LDS>
+__device__ __forceinline__ uint32_t* raster_begin(uint32_t* gmask, size_t words, int nmasks) {
+    extern __shared__ uint32_t s_mask[];
+    if (!LDS) return gmask;
+    for (size_t k = threadIdx.x; k < words * nmasks; k += kRasterBlock) s_mask[k] = 0u;
+    __syncthreads();
+    return s_mask;
+}
+
+template <bool LDS>
+__device__ __forceinline__ void raster_end(uint32_t* gmask, size_t gstride, size_t words,
+                                           int nmasks) {
+    extern __shared__ uint32_t s_mask[];
+    if (!LDS) return;
+    __syncthreads();
+    for (int m = 0; m < nmasks; ++m)
+        for (size_t k = threadIdx.x; k < words; k += kRasterBlock) {
+            const uint32_t b = s_mask[(size_t)m * words + k];
+            if (b) mask_or<false>(gmask + (size_t)m * gstride + k, b);
+        }
+}
+
+// GUARD: every lane projects with the default math; only lanes whose pixel
+// lies inside the guard band of a decision (off_half / off_edge above: about
+// one lane in 10^6) are projected again exactly.  Without it every lane takes
+// the exact projection (ACM_RASTER_EXACT_ALL).  The masks are the same bytes.
+template <bool LDS, bool GUARD>
+__global__ __launch_bounds__(kRasterBlock) void k_projection_masks(
+    CamArg cam_in, CamArg cam_out, uint32_t W, uint32_t H, size_t n,
+    const double* __restrict__ pts, int layout, uint32_t* gmask, size_t gstride,
+    unsigned long long* __restrict__ kept_parts) {
+    __shared__ unsigned long long s_kept;
+    const uint32_t wpr = (W + 31u) / 32u;
+    const size_t words = (size_t)wpr * H;
+    if (threadIdx.x == 0) s_kept = 0ull;
+    uint32_t* mask = raster_begin<LDS>(gmask, words, 2);  // synchronises when LDS
+    const size_t mstride = LDS ? words : gstride;
+    const Cam<double> ci = make_cam<double>(cam_in), co = make_cam<double>(cam_out);
+    const double wd = (double)W, hd = (double)H;
+    unsigned long long kept = 0ull;
+    for (size_t i = (size_t)blockIdx.x * kRasterBlock + threadIdx.x; i < n;
+         i += (size_t)gridDim.x * kRasterBlock) {
+        double x, y, z;
+        if (layout == ACM_LAYOUT_AOS) load_point<ACM_LAYOUT_AOS>(pts, n, i, x, y, z);
+        else load_point<ACM_LAYOUT_SOA>(pts, n, i, x, y, z);
+        double ui, vi, uo, vo;
+        const uint8_t si = project_any<!GUARD>(cam_in.model, ci, x, y, z, ui, vi);
+        const uint8_t so = project_any<!GUARD>(cam_out.model, co, x, y, z, uo, vo);
+        if (si != ST_OK || so != ST_OK) continue;
+        if (GUARD) {
+            const bool safe = off_half(ui) && off_half(vi) && off_half(uo) && off_half(vo) &&
+                              off_edge(uo, wd) && off_edge(vo, hd);
+            if (!safe) {
+                project_any<true>(cam_in.model, ci, x, y, z, ui, vi);
+                project_any<true>(cam_out.model, co, x, y, z, uo, vo);
+            }
+        }
+        // :281-285 (a NaN coordinate fails every comparison: dropped)
+        if (uo >= 0.0 && uo < wd && vo >= 0.0 && vo < hd) {
+            ++kept;
+            draw_disc<LDS>(mask, wpr, (int)W, (int)H, ui, vi);
+            draw_disc<LDS>(mask + mstride, wpr, (int)W, (int)H, uo, vo);
+        }
+    }
+    if (!LDS) __syncthreads();  // s_kept = 0 (raster_begin synchronised otherwise)
+    if (kept) atomicAdd(&s_kept, kept);
+    raster_end<LDS>(gmask, gstride, words, 2);  // synchronises when LDS
+    if (!LDS) __syncthreads();
+    if (threadIdx.x == 0) kept_parts[blockIdx.x] = s_kept;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kRasterBlock) void k_raster_points(uint32_t W, uint32_t H, size_t n,
+                                                                const double* __restrict__ uv,
+                                                                uint32_t* gmask) {
+    const uint32_t wpr = (W + 31u) / 32u;
+    const size_t words = (size_t)wpr * H;
+    uint32_t* mask = raster_begin<LDS>(gmask, words, 1);
+    for (size_t i = (size_t)blockIdx.x * kRasterBlock + threadIdx.x; i < n;
+         i += (size_t)gridDim.x * kRasterBlock)
+        draw_disc<LDS>(mask, wpr, (int)W, (int)H, uv[2 * i], uv[2 * i + 1]);
+    raster_end<LDS>(gmask, words, words, 1);
+}
+
+// Bitmask -> the public byte mask (0 / 1), four pixels per lane (one 4-B store
+// when the mask's address allows it).  ACC: OR into the existing bytes.  The
+// first lane also adds the per-workgroup kept counts, in index order.
+__global__ __launch_bounds__(kBlock) void k_mask_expand(uint32_t W, uint32_t H,
+                                                        const uint32_t* __restrict__ bits,
+                                                        uint8_t* __restrict__ out, bool acc,
+                                                        bool aligned,
+                                                        const unsigned long long* __restrict__ parts,
+                                                        int nb, unsigned long long* n_kept) {
+    const size_t wpr = ((size_t)W + 31) / 32, total = (size_t)W * H;
+    if (n_kept && blockIdx.x == 0 && threadIdx.x == 0) {
+        unsigned long long s = acc ? *n_kept : 0ull;
+        for (int b = 0; b < nb; ++b) s += parts[b];
+        *n_kept = s;
+    }
+    const size_t p0 = ((size_t)blockIdx.x * kBlock + threadIdx.x) * 4;
+    if (p0 >= total) return;
+    uint8_t b[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const size_t p = p0 + k;
+        b[k] = 0;
+        if (p < total) {
+            const size_t y = p / W, x = p - y * W;
+            b[k] = (uint8_t)((bits[y * wpr + (x >> 5)] >> (x & 31)) & 1u);
+            if (acc) b[k] |= (uint8_t)(out[p] != 0);
+        }
+    }
+    if (aligned && p0 + 4 <= total) {
+        *reinterpret_cast<uint32_t*>(out + p0) =
+            (uint32_t)b[0] | ((uint32_t)b[1] << 8) | ((uint32_t)b[2] << 16) | ((uint32_t)b[3] << 24);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (p0 + k < total) out[p0 + k] = b[k];
+    }
+}
+
+// Overlay / comparison picture (:388-510): output colour over input colour
+// over the background (NULL = black).  `image` may be the background.
+struct Rgb3 {
+    uint8_t c[3];
+};
+__global__ __launch_bounds__(kBlock) void k_compose(size_t total, const uint8_t* __restrict__ min_,
+                                                    const uint8_t* __restrict__ mout, Rgb3 cin,
+                                                    Rgb3 cout, const uint8_t* bg, uint8_t* image) {
+    const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= total) return;
+    uint8_t r = 0, g = 0, b = 0;
+    if (mout && mout[p]) {
+        r = cout.c[0]; g = cout.c[1]; b = cout.c[2];
+    } else if (min_ && min_[p]) {
+        r = cin.c[0]; g = cin.c[1]; b = cin.c[2];
+    } else if (bg) {
+        r = bg[3 * p]; g = bg[3 * p + 1]; b = bg[3 * p + 2];
+    }
+    image[3 * p] = r;
+    image[3 * p + 1] = g;
+    image[3 * p + 2] = b;
+}
+
+// ------------------------------------------------------ PSNR / SSIM
+// calculate_psnr (:45-89) and calculate_ssim (:108-210), one pixel per lane.
+// PSNR's two sums are integers (uint64: exact).  SSIM: the reference's
+// operations in its order (gray = (0.299 r + 0.587 g + 0.114 b) as u8, 3 x 3
+// sums dy outer / dx inner, mu = sum / 9, the second pass' squares / 8) --
+// this file is built -ffp-contract=off and `/` is the IEEE division, so each
+// term equals the reference's bit for bit.  A workgroup adds its terms in a
+// fixed order (lane order inside a wave by shuffles, then wave order) and
+// k_image_quality_finish adds the workgroups' partials in index order: no
+// float atomics, the same bits on every run.
+__device__ __forceinline__ double gray_of(const uint8_t* __restrict__ img, size_t p) {
+    const double g = 0.299 * (double)img[3 * p] + 0.587 * (double)img[3 * p + 1] +
+                     0.114 * (double)img[3 * p + 2];
+    return (double)(uint8_t)(g < 0.0 ? 0.0 : g > 255.0 ? 255.0 : g);  // `as u8` (:204)
+}
+
+struct IqParts {  // workspace: four arrays of nb entries
+    unsigned long long *sse, *valid, *cnt;
+    double* ssim;
+};
+
+__global__ __launch_bounds__(kBlock) void k_image_quality(uint32_t W, uint32_t H,
+                                                          const uint8_t* __restrict__ a,
+                                                          const uint8_t* __restrict__ b,
+                                                          double* __restrict__ ssim_map,
+                                                          IqParts parts) {
+    __shared__ unsigned long long s_sse[kBlock / 64], s_valid[kBlock / 64], s_cnt[kBlock / 64];
+    __shared__ double s_ssim[kBlock / 64];
+    const size_t total = (size_t)W * H;
+    const size_t p = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    unsigned long long sse = 0ull, valid = 0ull, cnt = 0ull;
+    double term = 0.0;
+    if (p < total) {
+        const int a0 = a[3 * p], a1 = a[3 * p + 1], a2 = a[3 * p + 2];
+        const int b0 = b[3 * p], b1 = b[3 * p + 1], b2 = b[3 * p + 2];
+        if (a0 | a1 | a2 | b0 | b1 | b2) {  // :62-74
+            sse = (unsigned long long)((a0 - b0) * (a0 - b0) + (a1 - b1) * (a1 - b1) +
+                                       (a2 - b2) * (a2 - b2));
+            valid = 3ull;
+        }
+        const size_t y = p / W, x = p - y * W;
+        if (W >= 3 && H >= 3 && x >= 1 && x + 1 < W && y >= 1 && y + 1 < H) {  // :128-129
+            double v1[9], v2[9];
+            double sum1 = 0.0, sum2 = 0.0;
+#pragma unroll
+            for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+                for (int dx = -1; dx <= 1; ++dx) {
+                    const size_t q = (size_t)((long long)y + dy) * W + (size_t)((long long)x + dx);
+                    const int k = (dy + 1) * 3 + dx + 1;
+                    v1[k] = gray_of(a, q);
+                    v2[k] = gray_of(b, q);
+                    sum1 += v1[k];
+                    sum2 += v2[k];
+                }
+            const double mu1 = sum1 / 9.0, mu2 = sum2 / 9.0;
+            double s1 = 0.0, s2 = 0.0, s12 = 0.0;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {  // :157-169
+                const double d1 = v1[k] - mu1, d2 = v2[k] - mu2;
+                s1 += d1 * d1;
+                s2 += d2 * d2;
+                s12 += d1 * d2;
+            }
+            s1 /= 8.0;
+            s2 /= 8.0;
+            s12 /= 8.0;
+            const double c1 = (0.01 * 255.0) * (0.01 * 255.0), c2 = (0.03 * 255.0) * (0.03 * 255.0);
+            const double num = (2.0 * mu1 * mu2 + c1) * (2.0 * s12 + c2);
+            const double den = (mu1 * mu1 + mu2 * mu2 + c1) * (s1 + s2 + c2);
+            double t = __builtin_nan("");
+            if (den > 0.0) {  // :178-181
+                t = num / den;
+                term = t;
+                cnt = 1ull;
+            }
+            if (ssim_map) ssim_map[(y - 1) * ((size_t)W - 2) + (x - 1)] = t;
+        }
+    }
+    // fixed-order workgroup sums: xor butterflies inside each wave, then the
+    // waves in index order
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        term += __shfl_xor(term, o, 64);
+        sse += (unsigned long long)__shfl_xor((long long)sse, o, 64);
+        valid += (unsigned long long)__shfl_xor((long long)valid, o, 64);
+        cnt += (unsigned long long)__shfl_xor((long long)cnt, o, 64);
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_ssim[wid] = term;
+        s_sse[wid] = sse;
+        s_valid[wid] = valid;
+        s_cnt[wid] = cnt;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        unsigned long long e = 0ull, v = 0ull, c = 0ull;
+        for (int w = 0; w < kBlock / 64; ++w) {
+            t += s_ssim[w];
+            e += s_sse[w];
+            v += s_valid[w];
+            c += s_cnt[w];
+        }
+        parts.ssim[blockIdx.x] = t;
+        parts.sse[blockIdx.x] = e;
+        parts.valid[blockIdx.x] = v;
+        parts.cnt[blockIdx.x] = c;
+    }
+}
+
+// result = {sse, valid, ssim_sum, ssim_count}: lane t adds its contiguous
+// run of partials in index order, lane 0 the 256 runs in index order.
+__global__ __launch_bounds__(kBlock) void k_image_quality_finish(IqParts parts, size_t nb,
+                                                                 void* result) {
+    __shared__ unsigned long long s_e[kBlock], s_v[kBlock], s_c[kBlock];
+    __shared__ double s_t[kBlock];
+    const size_t chunk = (nb + kBlock - 1) / kBlock;
+    const size_t lo = threadIdx.x * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
+    double t = 0.0;
+    unsigned long long e = 0ull, v = 0ull, c = 0ull;
+    for (size_t k = lo; k < hi; ++k) {
+        t += parts.ssim[k];
+        e += parts.sse[k];
+        v += parts.valid[k];
+        c += parts.cnt[k];
+    }
+    s_t[threadIdx.x] = t;
+    s_e[threadIdx.x] = e;
+    s_v[threadIdx.x] = v;
+    s_c[threadIdx.x] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        t = 0.0;
+        e = v = c = 0ull;
+        for (int k = 0; k < kBlock; ++k) {
+            t += s_t[k];
+            e += s_e[k];
+            v += s_v[k];
+            c += s_c[k];
+        }
+        unsigned long long* r = (unsigned long long*)result;
+        r[0] = e;
+        r[1] = v;
+        *reinterpret_cast<double*>(r + 2) = t;
+        r[3] = c;
+    }
+}
+
 static unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 // Host-side per-camera constants folded into unused parameter slots before a
@@ -5643,6 +6054,224 @@ ACM_API int acm_undistort_image(const acm_camera* cam, const double* target_intr
                                t[1], t[2], t[3], image, output);
         return check_launch("acm_undistort_image");
     });
+}
+
+// ---- projection rasters / image quality (image_quality.rs)
+static int hip_rc(hipError_t e, const char* what);
+// workspace of the rasters: [input bitmask][output bitmask][kept counts]
+static size_t raster_mask_words(uint32_t width, uint32_t height) {
+    return (((size_t)width + 31) / 32) * height;
+}
+static size_t raster_mask_stride(uint32_t width, uint32_t height) {  // words, 16-B multiple
+    return (raster_mask_words(width, height) + 3) & ~(size_t)3;
+}
+
+constexpr uint32_t kMaxImageSide = 1u << 30;
+static int check_image_size(uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0 || width > kMaxImageSide || height > kMaxImageSide)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "width and height must be 1 .. 2^30");
+    return ACM_SUCCESS;
+}
+
+// Workgroups of a raster launch: every resident slot of the device, at most
+// one per kRasterBlock points.  The LDS form (lds_bytes > 0) needs the
+// kernel's dynamic LDS limit raised; on failure returns 0 (global path).
+static int raster_blocks(const void* kernel, size_t n, size_t lds_bytes) {
+    if (lds_bytes > 64u << 10) {
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds_bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return 0;
+        }
+    }
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, kRasterBlock,
+                                                     lds_bytes) != hipSuccess || per_cu <= 0) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    size_t b = (size_t)per_cu * cu_count();
+    if (b > (size_t)kRasterMaxBlocks) b = kRasterMaxBlocks;
+    const size_t need = (n + kRasterBlock - 1) / kRasterBlock;
+    if (b > need) b = need;
+    return (int)(b ? b : 1);
+}
+
+static int launch_mask_expand(uint32_t width, uint32_t height, const uint32_t* bits, uint8_t* mask,
+                              bool acc, const unsigned long long* parts, int nb,
+                              unsigned long long* n_kept, hipStream_t s) {
+    const size_t total = (size_t)width * height;
+    const size_t blocks = ((total + 3) / 4 + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffu) return fail(ACM_ERR_INVALID_ARGUMENT, "image too large");
+    hipLaunchKernelGGL(k_mask_expand, dim3((unsigned)blocks), dim3(kBlock), 0, s, width, height,
+                       bits, mask, acc, ((uintptr_t)mask & 3) == 0, parts, nb, n_kept);
+    return ACM_SUCCESS;
+}
+
+ACM_API size_t acm_projection_masks_workspace_size(uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0 || width > kMaxImageSide || height > kMaxImageSide) return 0;
+    return 2 * raster_mask_stride(width, height) * sizeof(uint32_t) +
+           (size_t)kRasterMaxBlocks * sizeof(unsigned long long);
+}
+
+ACM_API int acm_projection_masks(const acm_camera* input_cam, const acm_camera* output_cam,
+                                 uint32_t width, uint32_t height, size_t n,
+                                 const double* points_3d, int layout, int flags,
+                                 uint8_t* input_mask, uint8_t* output_mask, uint64_t* n_kept,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_cam(input_cam);
+    if (rc) return rc;
+    if ((rc = check_cam(output_cam))) return rc;
+    if ((rc = check_layout(layout))) return rc;
+    if ((rc = check_image_size(width, height))) return rc;
+    if (flags & ~(ACM_RASTER_ACCUMULATE | ACM_RASTER_EXACT_ALL))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "unknown flags");
+    if (!input_mask || !output_mask || !n_kept || !workspace || (n && !points_3d))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (workspace_bytes < acm_projection_masks_workspace_size(width, height))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "projection-masks workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const bool acc = (flags & ACM_RASTER_ACCUMULATE) != 0;
+    const size_t words = raster_mask_words(width, height), stride = raster_mask_stride(width, height);
+    uint32_t* bits = (uint32_t*)workspace;
+    unsigned long long* parts = (unsigned long long*)(bits + 2 * stride);
+    if ((rc = hip_rc(hipMemsetAsync(bits, 0, 2 * stride * sizeof(uint32_t), s), "hipMemsetAsync")))
+        return rc;
+    int nb = 0;
+    if (n) {
+        const size_t lds = 2 * words * sizeof(uint32_t);
+        const bool guard = (flags & ACM_RASTER_EXACT_ALL) == 0;
+        auto launch = [&](auto lds_c, auto guard_c) {
+            constexpr bool LDS = decltype(lds_c)::value, GUARD = decltype(guard_c)::value;
+            const void* k = (const void*)k_projection_masks<LDS, GUARD>;
+            nb = raster_blocks(k, n, LDS ? lds : 0);
+            if (nb <= 0) return;
+            hipLaunchKernelGGL((k_projection_masks<LDS, GUARD>), dim3(nb), dim3(kRasterBlock),
+                               LDS ? lds : 0, s, prep(*input_cam), prep(*output_cam), width,
+                               height, n, points_3d, layout, bits, stride, parts);
+        };
+        if (lds <= kRasterLdsBudget) {
+            if (guard) launch(std::true_type{}, std::true_type{});
+            else launch(std::true_type{}, std::false_type{});
+        }
+        if (nb <= 0) {  // the image is too large for LDS (or the device refused it)
+            if (guard) launch(std::false_type{}, std::true_type{});
+            else launch(std::false_type{}, std::false_type{});
+        }
+        if ((rc = check_launch("acm_projection_masks"))) return rc;
+    }
+    if ((rc = launch_mask_expand(width, height, bits, input_mask, acc, parts, nb,
+                                 (unsigned long long*)n_kept, s)))
+        return rc;
+    if ((rc = launch_mask_expand(width, height, bits + stride, output_mask, acc, nullptr, 0,
+                                 nullptr, s)))
+        return rc;
+    return check_launch("acm_projection_masks (expand)");
+}
+
+ACM_API int acm_raster_points(uint32_t width, uint32_t height, size_t n, const double* points_2d,
+                              int flags, uint8_t* mask, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    int rc = check_image_size(width, height);
+    if (rc) return rc;
+    if (flags & ~ACM_RASTER_ACCUMULATE) return fail(ACM_ERR_INVALID_ARGUMENT, "unknown flags");
+    if (!mask || !workspace || (n && !points_2d))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (workspace_bytes < acm_projection_masks_workspace_size(width, height))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "raster workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t words = raster_mask_words(width, height);
+    uint32_t* bits = (uint32_t*)workspace;
+    if ((rc = hip_rc(hipMemsetAsync(bits, 0, words * sizeof(uint32_t), s), "hipMemsetAsync")))
+        return rc;
+    if (n) {
+        const size_t lds = words * sizeof(uint32_t);
+        int nb = 0;
+        if (lds <= kRasterLdsBudget) nb = raster_blocks((const void*)k_raster_points<true>, n, lds);
+        if (nb > 0) {
+            hipLaunchKernelGGL(k_raster_points<true>, dim3(nb), dim3(kRasterBlock), lds, s, width,
+                               height, n, points_2d, bits);
+        } else {
+            nb = raster_blocks((const void*)k_raster_points<false>, n, 0);
+            hipLaunchKernelGGL(k_raster_points<false>, dim3(nb), dim3(kRasterBlock), 0, s, width,
+                               height, n, points_2d, bits);
+        }
+        if ((rc = check_launch("acm_raster_points"))) return rc;
+    }
+    if ((rc = launch_mask_expand(width, height, bits, mask, (flags & ACM_RASTER_ACCUMULATE) != 0,
+                                 nullptr, 0, nullptr, s)))
+        return rc;
+    return check_launch("acm_raster_points (expand)");
+}
+
+ACM_API int acm_compose_projection_image(uint32_t width, uint32_t height,
+                                         const uint8_t* input_mask, const uint8_t* output_mask,
+                                         const uint8_t input_rgb[3], const uint8_t output_rgb[3],
+                                         const uint8_t* background, uint8_t* image, void* stream) {
+    int rc = check_image_size(width, height);
+    if (rc) return rc;
+    if (!image || !input_rgb || !output_rgb) return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    const size_t total = (size_t)width * height;
+    const size_t blocks = (total + kBlock - 1) / kBlock;
+    if (blocks > 0x7fffffffu) return fail(ACM_ERR_INVALID_ARGUMENT, "image too large");
+    Rgb3 ci, co;
+    for (int k = 0; k < 3; ++k) {
+        ci.c[k] = input_rgb[k];
+        co.c[k] = output_rgb[k];
+    }
+    hipLaunchKernelGGL(k_compose, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream,
+                       total, input_mask, output_mask, ci, co, background, image);
+    return check_launch("acm_compose_projection_image");
+}
+
+static size_t image_quality_blocks(uint32_t width, uint32_t height) {
+    return ((size_t)width * height + kBlock - 1) / kBlock;
+}
+
+ACM_API size_t acm_image_quality_workspace_size(uint32_t width, uint32_t height) {
+    if (width == 0 || height == 0 || width > kMaxImageSide || height > kMaxImageSide) return 0;
+    return image_quality_blocks(width, height) * 4 * sizeof(double);
+}
+
+ACM_API int acm_image_quality(uint32_t width, uint32_t height, const uint8_t* img1,
+                              const uint8_t* img2, void* result, double* ssim_map,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_image_size(width, height);
+    if (rc) return rc;
+    if (!img1 || !img2 || !result || !workspace)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (workspace_bytes < acm_image_quality_workspace_size(width, height))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "image-quality workspace too small");
+    const size_t nb = image_quality_blocks(width, height);
+    if (nb > 0x7fffffffu) return fail(ACM_ERR_INVALID_ARGUMENT, "image too large");
+    hipStream_t s = (hipStream_t)stream;
+    IqParts parts;
+    parts.sse = (unsigned long long*)workspace;
+    parts.valid = parts.sse + nb;
+    parts.cnt = parts.valid + nb;
+    parts.ssim = (double*)(parts.cnt + nb);
+    hipLaunchKernelGGL(k_image_quality, dim3((unsigned)nb), dim3(kBlock), 0, s, width, height, img1,
+                       img2, ssim_map, parts);
+    hipLaunchKernelGGL(k_image_quality_finish, dim3(1), dim3(kBlock), 0, s, parts, nb, result);
+    return check_launch("acm_image_quality");
+}
+
+ACM_API int acm_image_quality_finish(const void* result_host, double* psnr, double* ssim) {
+    if (!result_host || !psnr || !ssim) return fail(ACM_ERR_INVALID_ARGUMENT, "NULL argument");
+    uint64_t sse, valid, count;
+    double sum;
+    const char* r = (const char*)result_host;
+    std::memcpy(&sse, r, 8);
+    std::memcpy(&valid, r + 8, 8);
+    std::memcpy(&sum, r + 16, 8);
+    std::memcpy(&count, r + 24, 8);
+    *psnr = INFINITY;  // :78-85
+    if (valid != 0) {
+        const double mse = (double)sse / (double)valid;
+        if (!(mse <= 1e-10)) *psnr = 10.0 * std::log10(255.0 * 255.0 / mse);  // :87
+    }
+    *ssim = count > 0 ? sum / (double)count : 1.0;  // :186-190
+    return ACM_SUCCESS;
 }
 
 static int hip_rc(hipError_t e, const char* what) {

@@ -618,6 +618,79 @@ ACM_API int acm_undistort_image(const acm_camera *cam, const double *target_intr
                                 int interpolation, const uint8_t *image,
                                 uint8_t *output, void *stream);
 
+/* util::image_quality (src/util/image_quality.rs): the projection rasters
+ * of compute_image_quality_metrics, the overlay picture and PSNR / SSIM.
+ *
+ * A raster is a SET of pixels: every projection is drawn as the 13 pixels
+ * with dx^2 + dy^2 <= 4 around (round(u), round(v)) (round half away from
+ * zero, then Rust's saturating `as i32`, NaN -> 0; :353-369), clipped to the
+ * image, in one colour -- so the result does not depend on the order of the
+ * points and a parallel scatter reproduces the reference's sequential loop
+ * byte for byte.  Masks are device uint8[height * width], row-major, 1 =
+ * drawn.  width and height are 1 .. 2^30.
+ *
+ * acm_projection_masks (:272-293 + :338-373): one pass over points_3d.  A
+ * point is kept iff the input AND the output model project it Ok and the
+ * output pixel lies in [0, width) x [0, height) (width / height are the
+ * reference image's size when there is one, else the input model's
+ * resolution; the cameras' own width / height are not read).  Kept points
+ * draw their input pixel into input_mask (not bounds-checked: drawing clips)
+ * and their output pixel into output_mask; *n_kept (device uint64) counts
+ * them.  Every decision (the filter's bounds test, round()) is that of the
+ * reference-exact projections (ACM_EXACT_MATH): by default each lane
+ * projects with the default math and only pixels within a guard band of a
+ * decision (2e-10 relative, from the default math's 1e-10 bound) are
+ * projected again exactly; ACM_RASTER_EXACT_ALL projects every point exactly
+ * (the same masks, byte for byte; for measurements).
+ * flags: ACM_RASTER_ACCUMULATE ORs into the masks and adds to *n_kept
+ * instead of overwriting them (chunks or shards of one point set).  n = 0 is
+ * valid: clear masks and a count of 0 (unchanged with the flag).
+ * The workspace (acm_projection_masks_workspace_size bytes, 16-B aligned)
+ * holds the two bitmasks and the per-workgroup counts.
+ *
+ * acm_raster_points (create_projection_image, :338-373): the raster of n
+ * given pixels (points_2d: 2N f64, interleaved), same workspace size.
+ *
+ * acm_compose_projection_image (:388-510): per pixel output_rgb where
+ * output_mask is set, else input_rgb where input_mask is set, else the
+ * background (device RGB8 height x width, NULL = black).  Either mask may be
+ * NULL (empty); `image` may be the background buffer itself. */
+enum { ACM_RASTER_ACCUMULATE = 1, ACM_RASTER_EXACT_ALL = 2 };
+ACM_API size_t acm_projection_masks_workspace_size(uint32_t width, uint32_t height);
+ACM_API int acm_projection_masks(const acm_camera *input_cam, const acm_camera *output_cam,
+                                 uint32_t width, uint32_t height, size_t n,
+                                 const double *points_3d, int layout, int flags,
+                                 uint8_t *input_mask, uint8_t *output_mask, uint64_t *n_kept,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+ACM_API int acm_raster_points(uint32_t width, uint32_t height, size_t n,
+                              const double *points_2d, int flags, uint8_t *mask,
+                              void *workspace, size_t workspace_bytes, void *stream);
+ACM_API int acm_compose_projection_image(uint32_t width, uint32_t height,
+                                         const uint8_t *input_mask, const uint8_t *output_mask,
+                                         const uint8_t input_rgb[3], const uint8_t output_rgb[3],
+                                         const uint8_t *background, uint8_t *image, void *stream);
+
+/* calculate_psnr (:45-89) and calculate_ssim (:108-210) of two device RGB8
+ * images (height x width x 3).  result (device, 32 B):
+ *   uint64 sse        sum of squared channel differences over the pixel pairs
+ *                     that are not black in both images
+ *   uint64 valid      3 x the number of those pairs
+ *   double ssim_sum   sum of the per-pixel SSIM terms of the interior pixels
+ *   uint64 ssim_count number of those terms ((width - 2)(height - 2), or 0)
+ * ssim_map (nullable): the (height - 2) x (width - 2) per-pixel terms, each
+ * bit-identical to the reference's (no FMA contraction, IEEE divisions).
+ * ssim_sum adds per-workgroup partials in index order: the same bits on every
+ * run, and within count x 2^-53 of the reference's row-major sum.
+ * acm_image_quality_finish (host only): the reference's last steps on a host
+ * copy of `result` -- psnr = +inf when valid == 0 or sse / valid <= 1e-10,
+ * else 10 log10(255^2 / (sse / valid)) (bit-identical: both sums are exact
+ * integers); ssim = ssim_sum / ssim_count, or 1.0 when the count is 0. */
+ACM_API size_t acm_image_quality_workspace_size(uint32_t width, uint32_t height);
+ACM_API int acm_image_quality(uint32_t width, uint32_t height, const uint8_t *img1,
+                              const uint8_t *img2, void *result, double *ssim_map,
+                              void *workspace, size_t workspace_bytes, void *stream);
+ACM_API int acm_image_quality_finish(const void *result_host, double *psnr, double *ssim);
+
 /* Device-memory helpers so a host without HIP bindings (e.g. the Rust crate
  * through `extern "C"`) can own device buffers: thin wrappers over
  * hipMalloc / hipFree / hipMemcpyAsync / hipStreamSynchronize / hipSetDevice. */

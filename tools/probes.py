@@ -504,6 +504,83 @@ def probe_reproj_ceiling(argv):
                          40 + (8 if store else 0))
 
 
+def probe_projection_masks(argv):
+    """The per-point pass of compute_image_quality_metrics at config 5's point
+    set (1e8 cells -> 92.9M KB-sampled rays, KB -> the converted DS, 512 x 512):
+    acm_projection_masks (both exact projections, the filter and the two
+    rasters fused, 24 B read per point) against what a caller paid before it
+    existed just to obtain the two pixel sets -- two acm_project launches with
+    ACM_EXACT_MATH and no Jacobian (24 B read + 17 B written per point each;
+    acm_project itself is untouched).  Both variants of the fused pass: the
+    default (default math, exact only inside the guard band of a decision)
+    and ACM_RASTER_EXACT_ALL.  Interleaved rounds, event-timed;
+    reports every round, the best, and N * 24 B / t as a fraction of 8 TB/s.
+    Also timed, to place the cost: the same pass on the global path (the
+    same cameras under a 2048 x 2048 "reference image") and through two
+    pinholes (no atan2, no square root: the raster and the stream alone).
+
+      python tools/probes.py projection_masks [--cells N] [--reps R] [--rounds K]"""
+    ap = argparse.ArgumentParser(prog="probes.py projection_masks")
+    ap.add_argument("--cells", type=int, default=100_000_000)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--rounds", type=int, default=3)
+    a = ap.parse_args(argv)
+    import torch
+    from apex_camera_models import (KannalaBrandtModel, PinholeModel, Resolution, conversion,
+                                    samples, util)
+    kp, (w, h) = samples.SAMPLES[2]
+    src = KannalaBrandtModel._from_params(kp, Resolution(w, h))
+    uv, xyz = util.sample_points(src, a.cells)
+    n = xyz.shape[0]
+    dst = conversion.convert(src, "double_sphere", xyz, uv).model
+    del uv
+    pin = PinholeModel._from_params(list(kp[:4]), Resolution(w, h))
+    pin2 = PinholeModel._from_params([kp[0] * 1.01, kp[1] * 0.99, kp[2] + 0.4, kp[3] - 0.3],
+                                     Resolution(w, h))
+    out_uv = torch.empty((n, 2), dtype=torch.float64, device="cuda")
+    out_st = torch.empty((n,), dtype=torch.uint8, device="cuda")
+
+    def timed(fn):
+        fn()
+        e0 = torch.cuda.Event(enable_timing=True)
+        e1 = torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.reps
+
+    calls = {
+        "projection_masks": lambda: util.projection_masks(src, dst, xyz, w, h),
+        "projection_masks_exact_all": lambda: util.projection_masks(src, dst, xyz, w, h,
+                                                                    exact_all=True),
+        "project_exact_input": lambda: src.project_batch(xyz, out=(out_uv, out_st, None),
+                                                         exact=True),
+        "project_exact_output": lambda: dst.project_batch(xyz, out=(out_uv, out_st, None),
+                                                          exact=True),
+        "projection_masks_global_2048": lambda: util.projection_masks(src, dst, xyz, 2048, 2048),
+        "projection_masks_pinholes": lambda: util.projection_masks(pin, pin2, xyz, w, h),
+    }
+    ms = {k: [] for k in calls}
+    for _ in range(a.rounds):
+        for k, fn in calls.items():
+            ms[k].append(timed(fn))
+    best = {k: min(v) for k, v in ms.items()}
+    kept = int(util.projection_masks(src, dst, xyz, w, h)[2].item())
+    two = best["project_exact_input"] + best["project_exact_output"]
+    print(json.dumps({
+        "what": "fused projection masks vs two exact acm_project launches (ms, event-timed)",
+        "points": n, "kept": kept, "host": socket.gethostname(), "reps": a.reps,
+        "rounds_ms": {k: [round(x, 3) for x in v] for k, v in ms.items()},
+        "best_ms": {k: round(v, 3) for k, v in best.items()},
+        "two_projects_best_ms": round(two, 3),
+        "masks_over_two_projects": round(best["projection_masks"] / two, 3),
+        "masks_read_TBps": round(24.0 * n / best["projection_masks"] / 1e9, 3),
+        "masks_fraction_of_8TBps": round(24.0 * n / best["projection_masks"] / 1e9 / 8.0, 4),
+    }), flush=True)
+
+
 def probe_round_trip(argv):
     """Config-4 round trip (acm_project_unproject) A/B over ACM_TUNE_ROUND_TRIP
     settings (points per lane, LDS-staged or direct ray stores): every model at
