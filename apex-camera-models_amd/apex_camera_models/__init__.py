@@ -15,10 +15,11 @@ from .camera import (CameraModel, CameraModelError, DoubleSphereModel, EucmModel
                      Resolution, UcmModel)
 from .util import (ImageQualityMetrics, calculate_psnr, calculate_ssim,  # noqa: E402
                    compute_image_quality_metrics)
+from .optimizer import Pose, refine_pose  # noqa: E402
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
     "EucmModel", "FovModel", "Intrinsics", "KannalaBrandtModel", "PinholeModel", "RadTanModel",
     "Resolution", "UcmModel", "ImageQualityMetrics", "calculate_psnr", "calculate_ssim",
-    "compute_image_quality_metrics",
+    "compute_image_quality_metrics", "Pose", "refine_pose",
 ]

@@ -87,6 +87,14 @@ class AcmCollective(ctypes.Structure):
 RCCL_UNIQUE_ID_BYTES = 128
 
 
+class AcmPose(ctypes.Structure):
+    """acm_pose (include/acm.h): p_cam = R p_world + t, R row-major."""
+    _fields_ = [
+        ("r", ctypes.c_double * 9),
+        ("t", ctypes.c_double * 3),
+    ]
+
+
 class CellGrid(ctypes.Structure):
     """acm_cell_grid (include/acm.h, r06): the grid of a cell-form sample."""
     _fields_ = [
@@ -128,6 +136,7 @@ EXPORTED_SYMBOLS = (
     "acm_validate_params",
     "acm_project",
     "acm_project_f32",
+    "acm_project_point_jacobian",
     "acm_unproject",
     "acm_residual_jacobian",
     "acm_normal_equations_workspace_size",
@@ -160,6 +169,11 @@ EXPORTED_SYMBOLS = (
     "acm_reprojection_error_cells",
     "acm_linear_estimation_with_error_cells_async",
     "acm_lm_optimize_cells",
+    "acm_pose_retract",
+    "acm_pose_normal_equations_workspace_size",
+    "acm_pose_normal_equations",
+    "acm_pose_optimize_workspace_size",
+    "acm_pose_optimize",
     "acm_sample_points_cells",
     "acm_rccl_available",
     "acm_rccl_unique_id",
@@ -238,6 +252,8 @@ def load():
     L.acm_project.restype = i
     L.acm_project_f32.argtypes = [cam_p, sz, vp, i, vp, vp, vp, vp]
     L.acm_project_f32.restype = i
+    L.acm_project_point_jacobian.argtypes = [cam_p, sz, vp, i, vp, vp, vp, vp]
+    L.acm_project_point_jacobian.restype = i
     L.acm_unproject.argtypes = [cam_p, sz, vp, vp, i, vp, vp]
     L.acm_unproject.restype = i
     L.acm_residual_jacobian.argtypes = [cam_p, sz, vp, i, vp, i, vp, vp, vp, vp]
@@ -323,6 +339,18 @@ def load():
     L.acm_lm_optimize_cells.argtypes = [cam_p, sz, vp, i, vp, grid_p, ctypes.POINTER(LmConfig),
                                         ALLREDUCE_FN, vp, ctypes.POINTER(LmSummary), vp, sz, vp]
     L.acm_lm_optimize_cells.restype = i
+    pose_p = ctypes.POINTER(AcmPose)
+    L.acm_pose_retract.argtypes = [pose_p, ctypes.POINTER(ctypes.c_double)]
+    L.acm_pose_retract.restype = i
+    L.acm_pose_normal_equations_workspace_size.argtypes = [sz]
+    L.acm_pose_normal_equations_workspace_size.restype = sz
+    L.acm_pose_normal_equations.argtypes = [cam_p, pose_p, sz, vp, i, vp, vp, vp, sz, vp]
+    L.acm_pose_normal_equations.restype = i
+    L.acm_pose_optimize_workspace_size.argtypes = [sz]
+    L.acm_pose_optimize_workspace_size.restype = sz
+    L.acm_pose_optimize.argtypes = [cam_p, pose_p, sz, vp, i, vp, ctypes.POINTER(LmConfig),
+                                    ALLREDUCE_FN, vp, ctypes.POINTER(LmSummary), vp, sz, vp]
+    L.acm_pose_optimize.restype = i
     L.acm_sample_points_cells.argtypes = [cam_p, sz, sz, sz, i, vp, vp, vp, vp, vp, sz, vp]
     L.acm_sample_points_cells.restype = i
     L.acm_reprojection_error_cells.argtypes = [cam_p, sz, vp, i, vp, grid_p, vp, vp, vp, sz, vp]

@@ -239,6 +239,39 @@ class CameraModel:
                       jac.data_ptr() if jac is not None else None, _stream_handle()))
         return uv, st, jac
 
+    def project_point_jacobian_batch(self, points_3d, layout: str = "aos", exact: bool = False,
+                                     out: Optional[Tuple[torch.Tensor, ...]] = None):
+        """`project_batch` plus the derivative with respect to the 3-D point
+        (acm_project_point_jacobian).  Returns (uv (N,2), status (N,) uint8,
+        jac (3,N,2)): jac[c, i] = d(u, v)/d(x, y, z)[c] of point i -- memory
+        identical to a 2N x 3 column-major matrix, the view convention of
+        project_batch(jacobian=True).  uv and status are bit-identical to
+        project_batch's; failed points: uv = NaN, J = 0.  out = (uv, status,
+        jac): preallocated float64 outputs (uv and jac 16-B aligned)."""
+        lay = _lib.LAYOUT_SOA if layout == "soa" else _lib.LAYOUT_AOS
+        pts = points_3d if isinstance(points_3d, torch.Tensor) else torch.as_tensor(
+            points_3d, dtype=torch.float64)
+        pts = pts.to("cuda", torch.float64)
+        if lay == _lib.LAYOUT_SOA:
+            pts = pts.reshape(3, -1).contiguous()
+            n = pts.shape[1]
+        else:
+            pts = pts.reshape(-1, 3).contiguous()
+            n = pts.shape[0]
+        if out is not None:
+            uv, st, jac = out
+        else:
+            uv = torch.empty((n, 2), dtype=torch.float64, device=pts.device)
+            st = torch.empty((n,), dtype=torch.uint8, device=pts.device)
+            jac = torch.empty((3, n, 2), dtype=torch.float64, device=pts.device)
+        cam = self.acm_camera()
+        if exact:
+            lay |= _lib.EXACT_MATH
+        _lib.check(_lib.load().acm_project_point_jacobian(
+            ctypes.byref(cam), n, pts.data_ptr(), lay, uv.data_ptr(), st.data_ptr(),
+            jac.data_ptr(), _stream_handle()))
+        return uv, st, jac
+
     def unproject_batch(self, points_2d, layout: str = "aos", reference_newton: bool = False,
                         out: Optional[Tuple[Optional[torch.Tensor], ...]] = None):
         """Batched `CameraModel::unproject` (mod.rs:271).  Returns (rays, status).

@@ -145,3 +145,90 @@ class LevenbergMarquardt:
                         termination=_lib.LM_TERMINATION.get(summ.termination, "?"),
                         evaluations=summ.evaluations, initial_cost=summ.initial_cost,
                         final_cost=summ.final_cost, n_valid=int(summ.n_valid))
+
+
+class Pose:
+    """World -> camera rigid transform, p_cam = R p_world + t (acm_pose):
+    `rotation` a 3x3 nested list (row-major), `translation` a 3-list."""
+
+    def __init__(self, rotation=None, translation=None):
+        rot = [[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, 1.0]] if rotation is None else rotation
+        flat = [float(v) for row in rot for v in (row if hasattr(row, "__len__") else [row])]
+        if len(flat) != 9:
+            raise ValueError("rotation must be 3x3")
+        tr = [0.0, 0.0, 0.0] if translation is None else [float(v) for v in translation]
+        if len(tr) != 3:
+            raise ValueError("translation must have 3 entries")
+        self.rotation = [flat[0:3], flat[3:6], flat[6:9]]
+        self.translation = tr
+
+    def acm_pose(self) -> _lib.AcmPose:
+        p = _lib.AcmPose()
+        for k in range(9):
+            p.r[k] = self.rotation[k // 3][k % 3]
+        for k in range(3):
+            p.t[k] = self.translation[k]
+        return p
+
+    @classmethod
+    def _from_acm(cls, p: _lib.AcmPose) -> "Pose":
+        return cls([list(p.r[0:3]), list(p.r[3:6]), list(p.r[6:9])], list(p.t))
+
+    def retract(self, delta: Sequence[float]) -> "Pose":
+        """The pose moved by the left perturbation delta = (rho, phi):
+        R <- Exp(phi) R, t <- Exp(phi) t + rho (acm_pose_retract)."""
+        if len(delta) != 6:
+            raise ValueError("delta must have 6 entries (rho, phi)")
+        p = self.acm_pose()
+        d = (ctypes.c_double * 6)(*[float(v) for v in delta])
+        _lib.check(_lib.load().acm_pose_retract(ctypes.byref(p), d))
+        return Pose._from_acm(p)
+
+
+def refine_pose(model: CameraModel, pose: Pose, points_world, points_2d,
+                config: Optional[LevenbergMarquardtConfig] = None, collective=None,
+                allreduce: Optional[Callable] = None,
+                bounds: Optional[Dict[int, Tuple[float, float]]] = None) -> Tuple[Pose, LmResult]:
+    """6-DoF pose refinement of a calibrated camera over the fused GPU pose
+    normal equations (acm_pose_optimize): minimises sum ||project(R X + t) -
+    obs||^2 from `pose`.  Points that do not project, or whose observation is
+    NaN, are skipped.  collective / allreduce as LevenbergMarquardt.optimize
+    (the 44-double vector of every evaluation is summed across the ranks).
+    A local perturbation has no box: bounds raise."""
+    L = _lib.load()
+    p3 = _as_device_f64(points_world, 3)
+    p2 = _as_device_f64(points_2d, 2)
+    n = p3.shape[0]
+    if p2.shape[0] != n:
+        raise ValueError("points_world and points_2d must have the same number of points")
+    cfg = _lib.LmConfig()
+    L.acm_lm_default_config(ctypes.byref(cfg))
+    c = config or LevenbergMarquardtConfig()
+    cfg.max_iterations = c.max_iterations
+    cfg.cost_tolerance = c.cost_tolerance
+    cfg.parameter_tolerance = c.parameter_tolerance
+    cfg.gradient_tolerance = c.gradient_tolerance
+    cfg.initial_damping = c.initial_damping
+    if bounds:
+        cfg.has_bounds = 1  # rejected by the library (ACM_ERR_INVALID_ARGUMENT)
+    ws_bytes = L.acm_pose_optimize_workspace_size(n)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device=p3.device)
+    cam = model.acm_camera()
+    ap = pose.acm_pose()
+    summ = _lib.LmSummary()
+    ctx = None
+    if collective is not None:
+        cb, ctx = collective.c.allreduce, collective.c.ctx
+    elif allreduce is not None:
+        cb = _lib.ALLREDUCE_FN(allreduce)
+    else:
+        cb = _lib.ALLREDUCE_FN()
+    _lib.check(L.acm_pose_optimize(ctypes.byref(cam), ctypes.byref(ap), n,
+                                   p3.data_ptr() if n else None, _lib.LAYOUT_AOS,
+                                   p2.data_ptr() if n else None, ctypes.byref(cfg), cb, ctx,
+                                   ctypes.byref(summ), ws.data_ptr(), ws_bytes, _stream_handle()))
+    return Pose._from_acm(ap), LmResult(
+        parameters=list(ap.r) + list(ap.t), iterations=summ.iterations,
+        termination=_lib.LM_TERMINATION.get(summ.termination, "?"),
+        evaluations=summ.evaluations, initial_cost=summ.initial_cost,
+        final_cost=summ.final_cost, n_valid=int(summ.n_valid))

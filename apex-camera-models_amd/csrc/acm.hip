@@ -591,6 +591,80 @@ static void launch_al(hipStream_t s, const CamArg& cam, size_t n, const double* 
                        out2, status, jac);
 }
 
+// ------------------------------------- project + point Jacobian d(u,v)/d(x,y,z)
+// acm_project_point_jacobian: uv, status and the 2N x 3 column-major block
+// [du/dx dv/dx | du/dy dv/dy | du/dz dv/dz] (camera_models.hpp project<..,
+// PJ>), 24 B in and 16 + 1 + 48 B out per point.  The three columns are
+// 16-B-element streams at a 16 N byte stride like k_project_al's, so the
+// same windows: workgroup b owns points [256 b, 256 b + 256), lanes 0..7
+// also evaluate the 8 points before them, and a stream sitting sh (0..7)
+// elements off the 128-B grid is written by lane t as element 256 b - sh + t
+// from LDS, so every 128-B line of every stream is written whole by one
+// workgroup.  BASE_AL: uv and column 0 start on a line (sh = 0) and are
+// stored straight from registers.  uv and status are project<false, false,
+// EXACT>'s: the same bits as acm_project.
+template <class TagT, int LAYOUT, bool EXACT, bool BASE_AL>
+__global__ __launch_bounds__(kBlock) void k_project_pj_al(CamArg cam, size_t n,
+                                                          const double* __restrict__ pts,
+                                                          double* __restrict__ uv,
+                                                          uint8_t* __restrict__ status,
+                                                          double* __restrict__ jac) {
+    using M = typename TagT::template type<double>;
+    constexpr int S = kAlOwn + kAlLead;  // LDS slots: own points, then the lead-in
+    constexpr int NW = BASE_AL ? 1 : S;
+    __shared__ double2 s_uv[NW];
+    __shared__ double2 s_j0[NW];
+    __shared__ double2 s_j[2][S];
+    const Cam<double> c = make_cam<double>(cam);
+    const int t = threadIdx.x;
+    const size_t base = (size_t)blockIdx.x * kAlOwn;
+    auto eval = [&](size_t p, bool have, int slot, bool own) {
+        double x = 0.0, y = 0.0, z = 1.0;
+        if (have) load_point<LAYOUT>(pts, n, p, x, y, z);
+        double u, v, ju[3], jv[3];
+        const uint8_t st = M::template project<false, false, EXACT, true>(c, x, y, z, u, v, ju, jv);
+        const bool ok = have && st == ST_OK;
+        const double2 w = make_double2(ok ? u : __builtin_nan(""), ok ? v : __builtin_nan(""));
+        const double2 j0 = make_double2(ok ? ju[0] : 0.0, ok ? jv[0] : 0.0);
+        if (BASE_AL) {
+            if (own && have) {
+                st2<true>(uv + 2 * p, w.x, w.y);
+                st2<true>(jac + 2 * p, j0.x, j0.y);
+            }
+        } else {
+            s_uv[slot] = w;
+            s_j0[slot] = j0;
+        }
+        s_j[0][slot] = make_double2(ok ? ju[1] : 0.0, ok ? jv[1] : 0.0);
+        s_j[1][slot] = make_double2(ok ? ju[2] : 0.0, ok ? jv[2] : 0.0);
+        if (own && have) st1<true>(status + p, st);
+    };
+    // lead-in point k (0..7) = base - 8 + k, in slot kAlOwn + k
+    eval(base + t, base + t < n, t, true);
+    if (t < kAlLead)
+        eval(base + t - kAlLead, base >= (size_t)kAlLead && base + t - kAlLead < n, kAlOwn + t,
+             false);
+    __syncthreads();
+    // element e = base - sh + t of a stream sh elements off the line grid: own
+    // point base + t - sh (slot t - sh) or lead-in slot S - sh + t
+    size_t e;
+    int j;
+    auto elem = [&](unsigned sh) {
+        j = t >= (int)sh ? t - (int)sh : S - (int)sh + t;
+        e = base + t - sh;
+        return base + t >= sh && e < n;
+    };
+    if (!BASE_AL) {
+        if (elem(misalign16(uv, 0))) st2<true>(uv + 2 * e, s_uv[j].x, s_uv[j].y);
+        if (elem(misalign16(jac, 0))) st2<true>(jac + 2 * e, s_j0[j].x, s_j0[j].y);
+    }
+#pragma unroll
+    for (int col = 1; col < 3; ++col) {
+        if (!elem(misalign16(jac, (size_t)col * n))) continue;
+        st2<true>(jac + (size_t)col * 2 * n + 2 * e, s_j[col - 1][j].x, s_j[col - 1][j].y);
+    }
+}
+
 // --------------------------------------------------------------- unproject
 template <bool NT>
 __device__ __forceinline__ void st1d(double* p, double v) {
@@ -1377,6 +1451,117 @@ __global__ __launch_bounds__(kBlock) void k_ne_finish_cols(const double* __restr
 __global__ void k_ne_publish(unsigned long long* __restrict__ flag, unsigned long long seq) {
     __threadfence_system();
     __hip_atomic_store(flag, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ------------------------------------------------ pose normal equations
+// acm_pose_normal_equations: the camera fixed, the unknown a left
+// perturbation delta = (rho, phi) of the pose (R, t).  Per point
+//   p = R X + t,   r = project(p) - obs,   J = Jp [ I | -[p]x ]   (2 x 6)
+// with Jp = d(u, v)/dp (project<.., PJ>; FAST like k_normal_eq): row a of Jp
+// gives the row (a, p x a).  The pose arrives by value (SGPRs).  Per lane
+// the 21 upper-triangle sums of J^T J, the 6 of J^T r, r.r and n_valid (29);
+// workgroup sums by block_sum_store, column-major partials, and
+// k_pose_ne_finish sums each column in a fixed order: bit-reproducible.  A
+// point whose projection is not Ok or whose observation is NaN is skipped.
+// 40 B per point read (two points' loads in flight behind the current one's
+// math), nothing per point written.
+constexpr int kPoseK = 29;
+constexpr int kPoseAhead = 2;  // points in flight per lane
+
+template <class TagT, int LAYOUT>
+__global__ __launch_bounds__(kBlock) void k_pose_normal_eq(CamArg cam, acm_pose pose, size_t n,
+                                                           const double* __restrict__ pts,
+                                                           const double* __restrict__ obs,
+                                                           double* __restrict__ parts) {
+    using M = typename TagT::template type<double>;
+    const Cam<double> c = make_cam<double>(cam);
+    double acc[kPoseK];
+#pragma unroll
+    for (int k = 0; k < kPoseK; ++k) acc[k] = 0.0;
+    const size_t stride = (size_t)gridDim.x * kBlock;
+    size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    // One point per lane step, loads issued kPoseAhead steps ahead in static
+    // slots (normal_eq_body's U >= 3 form: a slot that is never moved keeps
+    // each wait the counted vmcnt of its own load).  Branch-free loads: past
+    // the end they read point n - 1 again, never accumulated.
+    double xs[kPoseAhead], ys[kPoseAhead], zs[kPoseAhead];
+    double2 os[kPoseAhead];
+    auto load_slot = [&](int q, size_t iq) {
+        const size_t ic = iq < n ? iq : n - 1;
+        load_point<LAYOUT, true>(pts, n, ic, xs[q], ys[q], zs[q]);
+        os[q] = ld2<true>(obs + 2 * ic);
+    };
+    auto accumulate = [&](double X, double Y, double Z, double2 o) {
+        const double px = pose.r[0] * X + pose.r[1] * Y + pose.r[2] * Z + pose.t[0];
+        const double py = pose.r[3] * X + pose.r[4] * Y + pose.r[5] * Z + pose.t[1];
+        const double pz = pose.r[6] * X + pose.r[7] * Y + pose.r[8] * Z + pose.t[2];
+        double u, v, ju[3], jv[3];
+        const uint8_t st = M::template project<false, true, false, true>(c, px, py, pz, u, v, ju, jv);
+        if (st == ST_OK && o.x == o.x && o.y == o.y) {
+            const double r0 = u - o.x, r1 = v - o.y;
+            const double a[6] = {ju[0], ju[1], ju[2], py * ju[2] - pz * ju[1],
+                                 pz * ju[0] - px * ju[2], px * ju[1] - py * ju[0]};
+            const double b[6] = {jv[0], jv[1], jv[2], py * jv[2] - pz * jv[1],
+                                 pz * jv[0] - px * jv[2], px * jv[1] - py * jv[0]};
+            int k = 0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+#pragma unroll
+                for (int q = r; q < 6; ++q, ++k) acc[k] = fma(a[r], a[q], fma(b[r], b[q], acc[k]));
+            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) acc[21 + r] = fma(a[r], r0, fma(b[r], r1, acc[21 + r]));
+            acc[27] = fma(r0, r0, fma(r1, r1, acc[27]));
+            acc[28] += 1.0;
+        }
+    };
+    if (n) {
+#pragma unroll
+        for (int q = 0; q < kPoseAhead; ++q) load_slot(q, i + (size_t)q * stride);
+    }
+    for (; i < n; i += (size_t)kPoseAhead * stride) {
+#pragma unroll
+        for (int q = 0; q < kPoseAhead; ++q) {
+            const size_t iq = i + (size_t)q * stride;
+            if (iq < n) accumulate(xs[q], ys[q], zs[q], os[q]);
+            load_slot(q, iq + (size_t)kPoseAhead * stride);
+        }
+    }
+    block_sum_store<kPoseK>(acc, parts + blockIdx.x, gridDim.x);
+}
+
+// Epilogue: workgroup k sums column k of the nb x 29 partials (lane l takes
+// rows l, l + 256, ... in order, the wave butterfly, the four waves in
+// order) and writes the entries of [JtJ (6 x 6, row-major, both triangles) |
+// Jtr (6) | 0.5 r.r | n_valid] that are that sum.
+__global__ __launch_bounds__(kBlock) void k_pose_ne_finish(const double* __restrict__ parts, int nb,
+                                                           double* __restrict__ out) {
+    const int k = blockIdx.x;
+    __shared__ double sm[kBlock / 64];
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nb; b += kBlock) a += parts[(size_t)k * nb + b];
+    a = wave_sum(a);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = a;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double S = 0.0;
+    for (int w = 0; w < kBlock / 64; ++w) S += sm[w];
+    if (k < 21) {
+        int r = 0, first = 0;  // row r of the upper triangle starts at sum `first`
+        while (k >= first + 6 - r) {
+            first += 6 - r;
+            ++r;
+        }
+        const int q = r + (k - first);
+        out[r * 6 + q] = S;
+        out[q * 6 + r] = S;
+    } else if (k < 27) {
+        out[36 + (k - 21)] = S;
+    } else if (k == 27) {
+        out[42] = 0.5 * S;
+    } else {
+        out[43] = S;
+    }
 }
 
 // ----------------------------------------------------- reprojection stats
@@ -5153,6 +5338,78 @@ ACM_API int acm_normal_equations_cells(const acm_camera* cam, size_t n, const do
     return acm::normal_equations_impl(cam, n, points_3d, layout, nullptr, invalid_policy,
                                       result, workspace, workspace_bytes, stream, nullptr, 0,
                                       nullptr, cells, grid, nullptr);
+}
+
+ACM_API int acm_project_point_jacobian(const acm_camera* cam, size_t n, const double* points_3d,
+                                       int layout, double* points_2d, uint8_t* status,
+                                       double* jacobian_point, void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    const bool exact = (layout & ACM_EXACT_MATH) != 0 &&
+                       (cam->model == ACM_KANNALA_BRANDT || cam->model == ACM_FOV);
+    layout &= ~ACM_EXACT_MATH;
+    if ((rc = check_layout(layout))) return rc;
+    if (n == 0) return ACM_SUCCESS;
+    if (!points_3d || !points_2d || !status || !jacobian_point)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if ((reinterpret_cast<uintptr_t>(points_2d) | reinterpret_cast<uintptr_t>(jacobian_point)) & 15u)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "points_2d and jacobian_point must be 16-B aligned");
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_model(cam->model, [&](auto tag) -> int {
+        using TagT = decltype(tag);
+        constexpr bool kHasExact = std::is_same<TagT, Tag<KannalaBrandt>>::value ||
+                                   std::is_same<TagT, Tag<Fov>>::value;
+        const bool al = al_base_aligned(points_2d, jacobian_point);
+        auto go = [&](auto lay_c, auto ex_c) {
+            constexpr int LAY = decltype(lay_c)::value;
+            constexpr bool EX = decltype(ex_c)::value;
+            auto kern = al ? k_project_pj_al<TagT, LAY, EX, true> : k_project_pj_al<TagT, LAY, EX, false>;
+            hipLaunchKernelGGL(kern, dim3(al_blocks(n)), dim3(kBlock), 0, s, prep(*cam), n,
+                               points_3d, points_2d, status, jacobian_point);
+        };
+        auto by_exact = [&](auto lay_c) {
+            if constexpr (kHasExact) {
+                if (exact) return go(lay_c, std::true_type{});
+            }
+            go(lay_c, std::false_type{});
+        };
+        if (layout == ACM_LAYOUT_AOS) by_exact(std::integral_constant<int, ACM_LAYOUT_AOS>{});
+        else by_exact(std::integral_constant<int, ACM_LAYOUT_SOA>{});
+        return check_launch("acm_project_point_jacobian");
+    });
+}
+
+ACM_API size_t acm_pose_normal_equations_workspace_size(size_t n) {
+    return ((size_t)nq_blocks(n) + 1) * (size_t)kPoseK * sizeof(double);
+}
+
+ACM_API int acm_pose_normal_equations(const acm_camera* cam, const acm_pose* pose, size_t n,
+                                      const double* points_world, int layout,
+                                      const double* points_2d_obs, double* result, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    if ((rc = check_layout(layout))) return rc;
+    if (!pose || !result || !workspace || (n && (!points_world || !points_2d_obs)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (workspace_bytes < acm_pose_normal_equations_workspace_size(n))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "pose normal-equations workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_model(cam->model, [&](auto tag) -> int {
+        using TagT = decltype(tag);
+        double* parts = (double*)workspace;
+        auto kern = layout == ACM_LAYOUT_AOS ? k_pose_normal_eq<TagT, ACM_LAYOUT_AOS>
+                                             : k_pose_normal_eq<TagT, ACM_LAYOUT_SOA>;
+        // at most the resident workgroups (resident_blocks): one round of
+        // dispatch, and a partition that depends only on n and the device
+        int nb = nq_blocks(n);
+        const int cap = resident_blocks(reinterpret_cast<const void*>(kern));
+        if (nb > cap) nb = cap;
+        hipLaunchKernelGGL(kern, dim3(nb), dim3(kBlock), 0, s, prep(*cam), *pose, n, points_world,
+                           points_2d_obs, parts);
+        hipLaunchKernelGGL(k_pose_ne_finish, dim3(kPoseK), dim3(kBlock), 0, s, parts, nb, result);
+        return check_launch("acm_pose_normal_equations");
+    });
 }
 
 ACM_API size_t acm_reprojection_stats_workspace_size(size_t n) {

@@ -58,6 +58,17 @@
 // mask (and n_valid) stays bit-exact.  Every other caller uses FAST = false,
 // the reference's operation order.
 //
+// project<WJ, FAST, EXACT, PJ>: PJ = true (acm_project_point_jacobian and the
+// pose normal equations; WJ = false) also returns the 2 x 3 derivative with
+// respect to the POINT, ju[0..3) = du/d(x, y, z), jv[0..3) = dv/d(x, y, z),
+// from the projection's own intermediates -- u, v and the status are the
+// same expressions as without it, so the same bits.  It is analytic and it
+// is the derivative of the branch the projection takes (KB's axis branch
+// returns the finite limit of the off-axis block, FOV's small-r branch the
+// derivative of its constant rd); formulas in DESIGN.md 8.1.  The reference
+// has no counterpart; tests hold it to 1e-10 of the point's largest entry
+// against 50-digit derivatives (observed < 1e-15).
+//
 // Reference citations: /root/reference/src/camera/<model>.rs:line.
 #pragma once
 
@@ -432,7 +443,7 @@ template <class T>
 struct Pinhole {
     static constexpr int P = 4;
     // pinhole.rs:165-182
-    template <bool WJ, bool FAST = false, bool EXACT = false>
+    template <bool WJ, bool FAST = false, bool EXACT = false, bool PJ = false>
     __device__ static __forceinline__ uint8_t project(const Cam<T>& c, T x, T y, T z, T& u,
                                                       T& v, T* ju, T* jv) {
         const T fx = c.p[0], fy = c.p[1], cx = c.p[2], cy = c.p[3];
@@ -461,6 +472,11 @@ struct Pinhole {
             ju[0] = xz; ju[1] = T(0); ju[2] = T(1); ju[3] = T(0);
             jv[0] = T(0); jv[1] = yz; jv[2] = T(0); jv[3] = T(1);
         }
+        if (PJ) {  // u = fx x / z + cx
+            const T r = FAST ? iz : rz;
+            ju[0] = fx * r; ju[1] = T(0); ju[2] = -(fxx * r);
+            jv[0] = T(0); jv[1] = fy * r; jv[2] = -(fyy * r);
+        }
         return st;
     }
     // pinhole.rs:228-246
@@ -485,18 +501,18 @@ template <class T>
 struct RadTan {
     static constexpr int P = 9;  // fx fy cx cy k1 k2 p1 p2 k3
     // rad_tan.rs:302-348
-    template <bool WJ, bool FAST = false, bool EXACT = false>
+    template <bool WJ, bool FAST = false, bool EXACT = false, bool PJ = false>
     __device__ static __forceinline__ uint8_t project(const Cam<T>& c, T x, T y, T z, T& u,
                                                       T& v, T* ju, T* jv) {
         const T fx = c.p[0], fy = c.p[1], cx = c.p[2], cy = c.p[3];
         const T k1 = c.p[4], k2 = c.p[5], p1 = c.p[6], p2 = c.p[7], k3 = c.p[8];
         const T iz = FAST ? T(1) / z : T(0);
-        T xp, yp;
+        T xp, yp, rz = T(0);
         if (FAST) {
             xp = x * iz;
             yp = y * iz;
         } else {
-            div2(x, y, z, xp, yp);  // x / z, y / z (:315-316)
+            rz = div2(x, y, z, xp, yp);  // x / z, y / z (:315-316)
         }
         T r2 = xp * xp + yp * yp;
         T r4 = r2 * r2;
@@ -523,6 +539,18 @@ struct RadTan {
             jv[6] = fy * (r2 + T(2) * yp * yp);
             jv[7] = fy * xpyp2;
             jv[8] = fy * yp * r6;
+        }
+        if (PJ) {
+            // d(xd, yd) / d(xp, yp) = [[a00, a01], [a01, a11]], then
+            // d(xp) = (1/z, 0, -xp/z), d(yp) = (0, 1/z, -yp/z)
+            const T r = FAST ? iz : rz;
+            const T dr = T(2) * (k1 + T(2) * k2 * r2 + T(3) * k3 * r4);  // d radial / d r2, doubled
+            const T a00 = radial + dr * xp * xp + T(2) * p1 * yp + T(6) * p2 * xp;
+            const T a01 = dr * xp * yp + T(2) * p1 * xp + T(2) * p2 * yp;
+            const T a11 = radial + dr * yp * yp + T(6) * p1 * yp + T(2) * p2 * xp;
+            const T fr = fx * r, gr = fy * r;
+            ju[0] = fr * a00; ju[1] = fr * a01; ju[2] = -(fr * (a00 * xp + a01 * yp));
+            jv[0] = gr * a01; jv[1] = gr * a11; jv[2] = -(gr * (a01 * xp + a11 * yp));
         }
         return st;
     }
@@ -768,7 +796,7 @@ template <class T>
 struct KannalaBrandt {
     static constexpr int P = 8;  // fx fy cx cy k1 k2 k3 k4
     // kannala_brandt.rs:340-394
-    template <bool WJ, bool FAST = false, bool EXACT = false>
+    template <bool WJ, bool FAST = false, bool EXACT = false, bool PJ = false>
     __device__ static __forceinline__ uint8_t project(const Cam<T>& c, T x, T y, T z, T& u,
                                                       T& v, T* ju, T* jv) {
         const T fx = c.p[0], fy = c.p[1], cx = c.p[2], cy = c.p[3];
@@ -825,6 +853,30 @@ struct KannalaBrandt {
             ju[4] = fxr * theta3; ju[5] = fxr * theta5; ju[6] = fxr * theta7; ju[7] = fxr * theta9;
             jv[0] = T(0); jv[1] = theta_d * y_r; jv[2] = T(0); jv[3] = T(1);
             jv[4] = fyr * theta3; jv[5] = fyr * theta5; jv[6] = fyr * theta7; jv[7] = fyr * theta9;
+        }
+        if (PJ) {
+            if (axis) {
+                // x_r = y_r = 0 here (u = cx, v = cy): the finite limit of the
+                // off-axis block as r -> 0, theta_d / r -> 1 / z
+                const T iz = T(1) / z;
+                ju[0] = fx * iz; ju[1] = T(0); ju[2] = T(0);
+                jv[0] = T(0); jv[1] = fy * iz; jv[2] = T(0);
+            } else {
+                // theta = atan2(r, z): d theta / dr = z / |p|^2, d theta / dz =
+                // -r / |p|^2; D = d theta_d / d theta.  With A = D z / |p|^2
+                // and B = theta_d / r:
+                //   d(theta_d x / r) / dx = A x_r^2 + B y_r^2
+                //   d(theta_d x / r) / dy = (A - B) x_r y_r
+                //   d(theta_d x / r) / dz = -D r / |p|^2 x_r
+                const T irr = kMul ? ir : T(1) / r;
+                const T in2 = T(1) / (r2 + z * z);
+                const T D = T(1) + T(3) * k1 * theta2 + T(5) * k2 * (theta2 * theta2) +
+                            T(7) * k3 * (theta3 * theta3) + T(9) * k4 * (theta5 * theta3);
+                const T A = D * z * in2, B = theta_d * irr, C = D * r * in2;
+                const T xx = x_r * x_r, yy = y_r * y_r, xy = x_r * y_r * (A - B);
+                ju[0] = fx * (A * xx + B * yy); ju[1] = fx * xy; ju[2] = -(fx * x_r * C);
+                jv[0] = fy * xy; jv[1] = fy * (A * yy + B * xx); jv[2] = -(fy * y_r * C);
+            }
         }
         return st;
     }
@@ -1190,12 +1242,26 @@ struct KannalaBrandt {
     }
 };
 
+// Point Jacobian of the unified-sphere family (DS, UCM, EUCM): u = fx x /
+// denom + cx, v = fy y / denom + cy with d denom / d(x, y, z) = (x kxy,
+// y kxy, kz); mx = x / denom, my = y / denom, id = 1 / denom.
+//   du/dx = fx (1 - mx x kxy) / denom    du/dy = -fx mx y kxy / denom
+//   du/dz = -fx mx kz / denom            (v alike)
+template <class T>
+__device__ __forceinline__ void denom_point_jacobian(T fx, T fy, T x, T y, T mx, T my, T id,
+                                                     T kxy, T kz, T* ju, T* jv) {
+    const T fi = fx * id, gi = fy * id;
+    const T xk = x * kxy, yk = y * kxy;
+    ju[0] = fi * (T(1) - mx * xk); ju[1] = -(fi * (mx * yk)); ju[2] = -(fi * (mx * kz));
+    jv[0] = -(gi * (my * xk)); jv[1] = gi * (T(1) - my * yk); jv[2] = -(gi * (my * kz));
+}
+
 // ---------------------------------------------------------- Double Sphere
 template <class T>
 struct DoubleSphere {
     static constexpr int P = 6;  // fx fy cx cy alpha xi
     // double_sphere.rs:361-390 + check_projection_condition :177-184
-    template <bool WJ, bool FAST = false, bool EXACT = false>
+    template <bool WJ, bool FAST = false, bool EXACT = false, bool PJ = false>
     __device__ static __forceinline__ uint8_t project(const Cam<T>& c, T x, T y, T z, T& u,
                                                       T& v, T* ju, T* jv) {
         const T fx = c.p[0], fy = c.p[1], cx = c.p[2], cy = c.p[3];
@@ -1229,6 +1295,15 @@ struct DoubleSphere {
             ju[4] = -tu * dda; ju[5] = -tu * ddx;
             jv[0] = T(0); jv[1] = my; jv[2] = T(0); jv[3] = T(1);
             jv[4] = -tv * dda; jv[5] = -tv * ddx;
+        }
+        if (PJ) {
+            // d denom / d(x, y) = (x, y) kxy, d denom / dz = kz with
+            // d gamma / d(x, y) = xi (x, y) / d1, d gamma / dz = xi z / d1 + 1
+            const T xd1 = xi / d1, ad2 = alpha / d2;
+            const T gz = xd1 * z + T(1);
+            const T kxy = ad2 * (T(1) + gamma * xd1) + (T(1) - alpha) * xd1;
+            const T kz = (ad2 * gamma + (T(1) - alpha)) * gz;
+            denom_point_jacobian(fx, fy, x, y, mx, my, FAST ? id : yd, kxy, kz, ju, jv);
         }
         return ok ? ST_OK : ST_POINT_IS_OUT_SIDE_IMAGE;
     }
@@ -1267,7 +1342,7 @@ template <class T>
 struct Ucm {
     static constexpr int P = 5;  // fx fy cx cy alpha
     // ucm.rs:297-316 + check_proj_condition :154-161
-    template <bool WJ, bool FAST = false, bool EXACT = false>
+    template <bool WJ, bool FAST = false, bool EXACT = false, bool PJ = false>
     __device__ static __forceinline__ uint8_t project(const Cam<T>& c, T x, T y, T z, T& u,
                                                       T& v, T* ju, T* jv) {
         const T fx = c.p[0], fy = c.p[1], cx = c.p[2], cy = c.p[3], alpha = c.p[4];
@@ -1291,6 +1366,11 @@ struct Ucm {
             T dda = d - z;
             ju[0] = mx; ju[1] = T(0); ju[2] = T(1); ju[3] = T(0); ju[4] = -tu * dda;
             jv[0] = T(0); jv[1] = my; jv[2] = T(0); jv[3] = T(1); jv[4] = -tv * dda;
+        }
+        if (PJ) {  // d denom / d(x, y) = alpha (x, y) / d, d denom / dz = alpha z / d + 1 - alpha
+            const T ad = alpha / d;
+            denom_point_jacobian(fx, fy, x, y, mx, my, FAST ? id : yd, ad,
+                                 ad * z + (T(1) - alpha), ju, jv);
         }
         return ok ? ST_OK : ST_POINT_IS_OUT_SIDE_IMAGE;
     }
@@ -1325,7 +1405,7 @@ template <class T>
 struct Eucm {
     static constexpr int P = 6;  // fx fy cx cy alpha beta
     // eucm.rs:328-347 + check_proj_condition :167-177
-    template <bool WJ, bool FAST = false, bool EXACT = false>
+    template <bool WJ, bool FAST = false, bool EXACT = false, bool PJ = false>
     __device__ static __forceinline__ uint8_t project(const Cam<T>& c, T x, T y, T z, T& u,
                                                       T& v, T* ju, T* jv) {
         const T fx = c.p[0], fy = c.p[1], cx = c.p[2], cy = c.p[3];
@@ -1358,6 +1438,11 @@ struct Eucm {
             ju[4] = -tu * dda; ju[5] = -tu * ddb;
             jv[0] = T(0); jv[1] = my; jv[2] = T(0); jv[3] = T(1);
             jv[4] = -tv * dda; jv[5] = -tv * ddb;
+        }
+        if (PJ) {  // d denom / d(x, y) = alpha beta (x, y) / d, d denom / dz = alpha z / d + 1 - alpha
+            const T ad = alpha / d;
+            denom_point_jacobian(fx, fy, x, y, mx, my, FAST ? id : yd, ad * beta,
+                                 ad * z + (T(1) - alpha), ju, jv);
         }
         return ok ? ST_OK : ST_POINT_IS_OUT_SIDE_IMAGE;
     }
@@ -1392,7 +1477,7 @@ template <class T>
 struct Fov {
     static constexpr int P = 5;  // fx fy cx cy w
     // fov.rs:284-316
-    template <bool WJ, bool FAST = false, bool EXACT = false>
+    template <bool WJ, bool FAST = false, bool EXACT = false, bool PJ = false>
     __device__ static __forceinline__ uint8_t project(const Cam<T>& c, T x, T y, T z, T& u,
                                                       T& v, T* ju, T* jv) {
         const T fx = c.p[0], fy = c.p[1], cx = c.p[2], cy = c.p[3], wf = c.p[4];
@@ -1419,6 +1504,22 @@ struct Fov {
             }
             ju[0] = mx; ju[1] = T(0); ju[2] = T(1); ju[3] = T(0); ju[4] = fx * x * drd;
             jv[0] = T(0); jv[1] = my; jv[2] = T(0); jv[3] = T(1); jv[4] = fy * y * drd;
+        }
+        if (PJ) {
+            if (axis) {  // rd is the constant 2 tan(w/2) / w in this branch
+                ju[0] = fx * rd; ju[1] = T(0); ju[2] = T(0);
+                jv[0] = T(0); jv[1] = fy * rd; jv[2] = T(0);
+            } else {
+                // rd = atan2(a, z) / (r w), a = 2 tan(w/2) r:
+                //   d rd / dr = (2 tan(w/2) z / (a^2 + z^2)) / (r w) - rd / r
+                //   d rd / dz = -2 tan(w/2) / (w (a^2 + z^2))
+                // and du/dx = fx (rd + x (x / r) d rd / dr), ...
+                const T a = T(2) * tan_w_half * r;
+                const T tw = T(2) * tan_w_half / (wf * (a * a + z * z));
+                const T g = (tw * z - rd) / r2;  // (d rd / dr) / r
+                ju[0] = fx * (rd + x * x * g); ju[1] = fx * (x * y * g); ju[2] = -(fx * x * tw);
+                jv[0] = fy * (x * y * g); jv[1] = fy * (rd + y * y * g); jv[2] = -(fy * y * tw);
+            }
         }
         return z < T(kEpsSqrt) ? ST_POINT_AT_CAMERA_CENTER : ST_OK;
     }

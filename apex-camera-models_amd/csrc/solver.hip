@@ -793,4 +793,110 @@ ACM_API int acm_lm_optimize_cells(acm_camera* cam, size_t n, const double* point
                        allreduce, allreduce_ctx, summary, workspace, workspace_bytes, stream);
 }
 
+// ------------------------------------------------------------- camera pose
+// R <- Exp(phi) R, t <- Exp(phi) t + rho with Exp(phi) = I + A K + B K^2,
+// K = [phi]x, A = sin(th) / th, B = (1 - cos(th)) / th^2.  B is taken as
+// 0.5 (sin(th/2) / (th/2))^2, so neither coefficient cancels; for th^2 < 1e-6
+// both are their series through th^4 (the next terms are < 1e-21).  Host
+// code in long double, rounded once per entry: the composed pose is within an
+// ulp or two of the exact product, and R stays orthonormal to a few eps per
+// step without re-orthonormalisation.
+ACM_API int acm_pose_retract(acm_pose* pose, const double delta[6]) {
+    if (!pose || !delta) return sfail(ACM_ERR_INVALID_ARGUMENT, "NULL argument");
+    typedef long double ld;
+    const ld px = delta[3], py = delta[4], pz = delta[5];
+    const ld t2 = px * px + py * py + pz * pz;
+    ld A, B;
+    if (t2 < 1e-6L) {
+        A = 1.0L - t2 / 6.0L + t2 * t2 / 120.0L;
+        B = 0.5L - t2 / 24.0L + t2 * t2 / 720.0L;
+    } else {
+        const ld th = sqrtl(t2), hf = 0.5L * th;
+        const ld sh = sinl(hf) / hf;
+        A = sinl(th) / th;
+        B = 0.5L * sh * sh;
+    }
+    // K^2 = phi phi^T - th^2 I
+    const ld E[9] = {1.0L - B * (py * py + pz * pz), B * px * py - A * pz, B * px * pz + A * py,
+                     B * px * py + A * pz, 1.0L - B * (px * px + pz * pz), B * py * pz - A * px,
+                     B * px * pz - A * py, B * py * pz + A * px, 1.0L - B * (px * px + py * py)};
+    acm_pose out;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j)
+            out.r[3 * i + j] = (double)(E[3 * i] * (ld)pose->r[j] + E[3 * i + 1] * (ld)pose->r[3 + j] +
+                                        E[3 * i + 2] * (ld)pose->r[6 + j]);
+        out.t[i] = (double)(E[3 * i] * (ld)pose->t[0] + E[3 * i + 1] * (ld)pose->t[1] +
+                            E[3 * i + 2] * (ld)pose->t[2] + (ld)delta[i]);
+    }
+    *pose = out;
+    return ACM_SUCCESS;
+}
+
+// LM workspace: the pose normal equations' partials | the 44 results (+ 4 spare)
+ACM_API size_t acm_pose_optimize_workspace_size(size_t n) {
+    return acm_pose_normal_equations_workspace_size(n) + 48 * sizeof(double);
+}
+
+// acm_lm_optimize's state machine (lm_core.hpp, P = 6) in local coordinates:
+// State::x only accumulates the accepted steps (it starts at 0, so the
+// parameter tolerance is relative to the distance moved); the evaluation the
+// machine asks for at xn = x + h is taken at retract(current pose, h), and
+// the current pose becomes that trial pose when consume() accepts the step
+// (x == the xn it asked for: a requested trial always has xn != x, or
+// advance() would have ended the run on the parameter tolerance).
+ACM_API int acm_pose_optimize(const acm_camera* cam, acm_pose* pose, size_t n,
+                              const double* points_world, int layout,
+                              const double* points_2d_obs, const acm_lm_config* cfg,
+                              acm_allreduce_fn allreduce, void* allreduce_ctx,
+                              acm_lm_summary* summary, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+    if (!cam || !pose || !cfg) return sfail(ACM_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (acm_num_params(cam->model) < 0) return sfail(ACM_ERR_INVALID_MODEL, "unknown camera model id");
+    if (cfg->has_bounds)
+        return sfail(ACM_ERR_INVALID_ARGUMENT, "pose optimisation takes no parameter bounds");
+    if (layout != ACM_LAYOUT_AOS && layout != ACM_LAYOUT_SOA)
+        return sfail(ACM_ERR_INVALID_ARGUMENT, "layout must be ACM_LAYOUT_AOS or ACM_LAYOUT_SOA");
+    if (n && (!points_world || !points_2d_obs)) return sfail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace || workspace_bytes < acm_pose_optimize_workspace_size(n))
+        return sfail(ACM_ERR_WORKSPACE_TOO_SMALL, "pose LM workspace too small");
+    constexpr int P = 6, R = P * P + P + 2;
+    const size_t ne_ws = acm_pose_normal_equations_workspace_size(n);
+    double* d_res = (double*)((char*)workspace + ne_ws);
+    hipStream_t s = (hipStream_t)stream;
+    const double zero[P] = {0, 0, 0, 0, 0, 0};
+    acm::lm::State st;
+    acm::lm::start(st, *cfg, P, zero);
+    acm_pose cur = *pose;
+    double res[R];
+    int r = acm::lm::NEED_EVAL;
+    while (r == acm::lm::NEED_EVAL) {
+        acm_pose trial = cur;
+        acm_pose_retract(&trial, st.h);  // h = 0 at the first evaluation: the start pose itself
+        int rc = acm_pose_normal_equations(cam, &trial, n, points_world, layout, points_2d_obs,
+                                           d_res, workspace, ne_ws, stream);
+        if (rc) return rc;
+        if (allreduce && allreduce(allreduce_ctx, d_res, (size_t)R, stream))
+            return sfail(ACM_ERR_HIP, "all-reduce callback failed");
+        if (hip_ok(hipMemcpyAsync(res, d_res, R * sizeof(double), hipMemcpyDeviceToHost, s)) ||
+            hip_ok(hipStreamSynchronize(s)))
+            return sfail(ACM_ERR_HIP, "pose LM: device copy failed");
+        const bool is_trial = st.phase == 1;
+        double asked[P];
+        std::memcpy(asked, st.xn, sizeof(asked));
+        r = acm::lm::consume(st, *cfg, res, P);
+        if (is_trial && std::memcmp(st.x, asked, sizeof(asked)) == 0) cur = trial;
+    }
+    *pose = cur;
+    acm_lm_summary sum;
+    std::memset(&sum, 0, sizeof(sum));
+    sum.iterations = st.it;
+    sum.termination = st.term;
+    sum.evaluations = st.evals;
+    sum.initial_cost = st.initial_cost;
+    sum.final_cost = st.F;
+    sum.n_valid = st.nv;
+    if (summary) *summary = sum;
+    return ACM_SUCCESS;
+}
+
 }  // extern "C"

@@ -165,6 +165,27 @@ ACM_API int acm_project_f32(const acm_camera *cam, size_t n,
                             const float *points_3d, int layout, float *points_2d,
                             uint8_t *status, float *jacobian, void *stream);
 
+/* acm_project plus the derivative with respect to the 3-D POINT: the 2 x 3
+ * block d(u, v)/d(x, y, z) per point (basalt's d_proj_d_p3d), what pose
+ * refinement, triangulation and bundle adjustment linearise with.
+ * points_3d, layout (optionally | ACM_EXACT_MATH), points_2d and status as
+ * acm_project, and bit-identical to what acm_project writes for the same
+ * arguments.  jacobian_point: 2N x 3 f64 out, column-major like the
+ * parameter Jacobian -- entry (2i + r, c) at [c * 2N + 2i + r], r = 0 (u),
+ * 1 (v), c = 0, 1, 2 for x, y, z.  Failed points: uv = NaN, J = 0; a point
+ * whose status is Ok has a finite block.  Analytic, the derivative of the
+ * branch the projection takes: KB at x = y = 0 returns the finite limit
+ * [[fx/z, 0, 0], [0, fy/z, 0]]; FOV inside r^2 < 1.49e-8 returns
+ * [[fx rd, 0, 0], [0, fy rd, 0]], rd = 2 tan(w/2) / w.  points_2d and
+ * jacobian_point must be 16-B aligned (any other offset is fine: every
+ * 128-B line of every output stream is stored whole by one workgroup).
+ * 89 B per point (24 in, 65 out); no allocation, stream-ordered,
+ * reentrant; n = 0 is valid. */
+ACM_API int acm_project_point_jacobian(const acm_camera *cam, size_t n,
+                                       const double *points_3d, int layout,
+                                       double *points_2d, uint8_t *status,
+                                       double *jacobian_point, void *stream);
+
 /* Batched CameraModel::unproject (mod.rs:271).  rays: 3N f64 out written in
  * `layout` (optionally | ACM_REFERENCE_NEWTON); failed points: ray = NaN. */
 ACM_API int acm_unproject(const acm_camera *cam, size_t n,
@@ -423,6 +444,47 @@ ACM_API int acm_linear_estimation_with_error_cells_async(
     acm_camera *cam, size_t n, const double *points_3d, int layout, const double *points_2d,
     const uint32_t *cells, const acm_cell_grid *grid, double *initial_error,
     double *initial_error_host, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Camera pose refinement (PnP refinement): the camera is fixed, the unknown
+ * is the rigid transform world -> camera, p_cam = R p_world + t.  r is the
+ * rotation matrix, row-major.  The perturbation is delta = (rho_x rho_y
+ * rho_z phi_x phi_y phi_z), applied on the left:
+ *   acm_pose_retract (host only):  R <- Exp(phi) R,  t <- Exp(phi) t + rho,
+ * Exp = Rodrigues' formula (a series for |phi|^2 < 1e-6, half-angle forms
+ * beyond: nothing cancels).
+ * acm_pose_normal_equations: per point p = R X + t, r = project(p) - obs,
+ * J = Jpoint(p) [ I | -[p]x ] (2 x 6), accumulated without materialising
+ * r, J or p.  result (device, 44 f64): [JtJ (6 x 6, row-major, symmetric) |
+ * Jtr (6) | cost = 0.5 sum ||r||^2 | n_valid] -- acm_normal_equations'
+ * layout with P = 6.  Points whose projection is not Ok, or whose
+ * observation is NaN, are skipped and not counted.  Deterministic (fixed
+ * per-workgroup partials + an ordered final sum: repeated calls return the
+ * same bits); 40 B per point read.  layout: ACM_LAYOUT_AOS / _SOA only.
+ * workspace (device): acm_pose_normal_equations_workspace_size bytes.
+ * acm_pose_optimize: acm_lm_optimize's state machine with P = 6 in local
+ * coordinates -- each trial step h is evaluated at retract(pose, h), and the
+ * pose moves when the step is accepted.  *pose: start in, optimum out.
+ * cfg->has_bounds != 0 is ACM_ERR_INVALID_ARGUMENT (a local perturbation has
+ * no box); cfg->invalid_policy is ignored (invalid points are skipped).
+ * allreduce (nullable) receives the 44-double device vector of every
+ * evaluation.  workspace (device): acm_pose_optimize_workspace_size bytes. */
+typedef struct acm_pose {
+    double r[9];
+    double t[3];
+} acm_pose;
+ACM_API int acm_pose_retract(acm_pose *pose, const double delta[6]);
+ACM_API size_t acm_pose_normal_equations_workspace_size(size_t n);
+ACM_API int acm_pose_normal_equations(const acm_camera *cam, const acm_pose *pose, size_t n,
+                                      const double *points_world, int layout,
+                                      const double *points_2d_obs, double *result,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+ACM_API size_t acm_pose_optimize_workspace_size(size_t n);
+ACM_API int acm_pose_optimize(const acm_camera *cam, acm_pose *pose, size_t n,
+                              const double *points_world, int layout,
+                              const double *points_2d_obs, const acm_lm_config *cfg,
+                              acm_allreduce_fn allreduce, void *allreduce_ctx,
+                              acm_lm_summary *summary, void *workspace,
+                              size_t workspace_bytes, void *stream);
 
 /* (r06) The sharded conversion's collectives.  One
  * process per GPU, each holding a shard of the correspondences; both

@@ -170,7 +170,7 @@ int acm_probe_mimic(size_t n, const double* xyz, double* uv, uint8_t* st, double
                                 xyz, uv, st, jac);                                        \
         return (int)hipGetLastError();                                                    \
     }
-    MIMIC(0) MIMIC(4) MIMIC(5) MIMIC(6) MIMIC(8) MIMIC(9)
+    MIMIC(0) MIMIC(3) MIMIC(4) MIMIC(5) MIMIC(6) MIMIC(8) MIMIC(9)
 #undef MIMIC
     return -1;
 }
