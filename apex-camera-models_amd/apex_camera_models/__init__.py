@@ -15,11 +15,13 @@ from .camera import (CameraModel, CameraModelError, DoubleSphereModel, EucmModel
                      Resolution, UcmModel)
 from .util import (ImageQualityMetrics, calculate_psnr, calculate_ssim,  # noqa: E402
                    compute_image_quality_metrics)
-from .optimizer import Pose, refine_pose  # noqa: E402
+from .optimizer import (Pose, TriangulationConfig, TriangulationResult, refine_pose,  # noqa: E402
+                        tracks_from_dense, triangulate)
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
     "EucmModel", "FovModel", "Intrinsics", "KannalaBrandtModel", "PinholeModel", "RadTanModel",
     "Resolution", "UcmModel", "ImageQualityMetrics", "calculate_psnr", "calculate_ssim",
-    "compute_image_quality_metrics", "Pose", "refine_pose",
+    "compute_image_quality_metrics", "Pose", "refine_pose", "triangulate", "tracks_from_dense",
+    "TriangulationConfig", "TriangulationResult",
 ]

@@ -95,6 +95,25 @@ class AcmPose(ctypes.Structure):
     ]
 
 
+class TriangulateConfig(ctypes.Structure):
+    """acm_triangulate_config (include/acm.h)."""
+    _fields_ = [
+        ("max_iterations", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("cost_tolerance", ctypes.c_double),
+        ("parameter_tolerance", ctypes.c_double),
+        ("gradient_tolerance", ctypes.c_double),
+        ("initial_damping", ctypes.c_double),
+        ("min_parallax_sin2", ctypes.c_double),
+    ]
+
+
+# acm_tri_status / flags / the per-wave LDS staging budget (include/acm.h)
+TRI_OK, TRI_TOO_FEW_OBSERVATIONS, TRI_DEGENERATE, TRI_NOT_CONVERGED = 0, 1, 2, 3
+TRI_USE_INITIAL = 1
+TRI_STAGE_OBSERVATIONS = 512
+
+
 class CellGrid(ctypes.Structure):
     """acm_cell_grid (include/acm.h, r06): the grid of a cell-form sample."""
     _fields_ = [
@@ -174,6 +193,9 @@ EXPORTED_SYMBOLS = (
     "acm_pose_normal_equations",
     "acm_pose_optimize_workspace_size",
     "acm_pose_optimize",
+    "acm_triangulate_default_config",
+    "acm_triangulate_workspace_size",
+    "acm_triangulate",
     "acm_sample_points_cells",
     "acm_rccl_available",
     "acm_rccl_unique_id",
@@ -351,6 +373,14 @@ def load():
     L.acm_pose_optimize.argtypes = [cam_p, pose_p, sz, vp, i, vp, ctypes.POINTER(LmConfig),
                                     ALLREDUCE_FN, vp, ctypes.POINTER(LmSummary), vp, sz, vp]
     L.acm_pose_optimize.restype = i
+    tri_p = ctypes.POINTER(TriangulateConfig)
+    L.acm_triangulate_default_config.argtypes = [tri_p]
+    L.acm_triangulate_default_config.restype = None
+    L.acm_triangulate_workspace_size.argtypes = [sz, sz]
+    L.acm_triangulate_workspace_size.restype = sz
+    L.acm_triangulate.argtypes = [cam_p, sz, vp, sz, vp, sz, vp, vp, tri_p, vp, vp, vp, vp, vp,
+                                  vp, sz, vp]
+    L.acm_triangulate.restype = i
     L.acm_sample_points_cells.argtypes = [cam_p, sz, sz, sz, i, vp, vp, vp, vp, vp, sz, vp]
     L.acm_sample_points_cells.restype = i
     L.acm_reprojection_error_cells.argtypes = [cam_p, sz, vp, i, vp, grid_p, vp, vp, vp, sz, vp]

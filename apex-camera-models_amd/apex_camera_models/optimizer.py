@@ -232,3 +232,111 @@ def refine_pose(model: CameraModel, pose: Pose, points_world, points_2d,
         termination=_lib.LM_TERMINATION.get(summ.termination, "?"),
         evaluations=summ.evaluations, initial_cost=summ.initial_cost,
         final_cost=summ.final_cost, n_valid=int(summ.n_valid))
+
+
+# ------------------------------------------------------------ triangulation
+@dataclass
+class TriangulationConfig:
+    """acm_triangulate_config; the defaults are acm_triangulate_default_config's."""
+    max_iterations: int = 20
+    cost_tolerance: float = 1e-6
+    parameter_tolerance: float = 1e-8
+    gradient_tolerance: float = 1e-6
+    initial_damping: float = 1e-4
+    min_parallax_sin2: float = 1e-8
+
+
+@dataclass
+class TriangulationResult:
+    """Device tensors, one row per point: points (N, 3) f64, status (N,) u8
+    (_lib.TRI_OK / TRI_TOO_FEW_OBSERVATIONS / TRI_DEGENERATE /
+    TRI_NOT_CONVERGED), cost (N,) f64, n_valid (N,) i32, information (N, 6)
+    f64 -- the upper triangle of J^T J, row by row -- or None."""
+    points: torch.Tensor
+    status: torch.Tensor
+    cost: torch.Tensor
+    n_valid: torch.Tensor
+    information: Optional[torch.Tensor]
+
+
+def _poses_tensor(poses) -> torch.Tensor:
+    """(K, 12) device f64, acm_pose's layout: R row-major, then t."""
+    if isinstance(poses, torch.Tensor):
+        t = poses
+        if t.device.type != "cuda":
+            t = t.to("cuda")
+        return t.to(torch.float64).reshape(-1, 12).contiguous()
+    rows = [[v for row in p.rotation for v in row] + list(p.translation) for p in poses]
+    return torch.tensor(rows, dtype=torch.float64, device="cuda").reshape(-1, 12)
+
+
+def tracks_from_dense(observations):
+    """CSR tracks of a dense observation tensor [K, N, 2] (view, point, uv):
+    entries with a NaN coordinate are dropped.  Returns (track_offsets (N + 1,)
+    int64, obs_view (M,) int32, obs_uv (M, 2) float64) on the device, each
+    point's observations in view order."""
+    obs = observations if isinstance(observations, torch.Tensor) else torch.as_tensor(observations)
+    if obs.device.type != "cuda":
+        obs = obs.to("cuda")
+    obs = obs.to(torch.float64)
+    if obs.dim() != 3 or obs.shape[2] != 2:
+        raise ValueError("observations must be [K, N, 2]")
+    per_point = obs.permute(1, 0, 2)                      # (N, K, 2)
+    seen = ~torch.isnan(per_point).any(dim=2)             # (N, K)
+    offsets = torch.zeros(per_point.shape[0] + 1, dtype=torch.int64, device=obs.device)
+    offsets[1:] = torch.cumsum(seen.sum(dim=1), dim=0)
+    idx = torch.nonzero(seen)                             # row-major: point, then view
+    return offsets, idx[:, 1].to(torch.int32).contiguous(), per_point[seen].contiguous()
+
+
+def triangulate(model: CameraModel, poses, track_offsets, obs_view, obs_uv, initial=None,
+                config: Optional[TriangulationConfig] = None,
+                want_information: bool = False) -> TriangulationResult:
+    """Batched multi-view triangulation (acm_triangulate): one 3-D point per
+    track from known world -> camera poses, by the midpoint of the unprojected
+    rays refined with a per-point Levenberg-Marquardt on the reprojection
+    error.  poses: a sequence of Pose or a (K, 12) tensor; track_offsets
+    (N + 1,) int64, obs_view (M,) int32, obs_uv (M, 2) f64: the CSR tracks
+    (tracks_from_dense builds them).  initial (N, 3): start the refinement
+    there instead of at the midpoint (ACM_TRI_USE_INITIAL); the caller's
+    tensor is not modified."""
+    L = _lib.load()
+    pt = _poses_tensor(poses)
+    offs = torch.as_tensor(track_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    view = torch.as_tensor(obs_view).to(device="cuda", dtype=torch.int32).contiguous()
+    uv = _as_device_f64(obs_uv, 2)
+    n = offs.shape[0] - 1
+    m = view.shape[0]
+    if n < 0 or uv.shape[0] != m:
+        raise ValueError("track_offsets needs N + 1 entries; obs_view and obs_uv one row per observation")
+    c = config or TriangulationConfig()
+    cfg = _lib.TriangulateConfig()
+    L.acm_triangulate_default_config(ctypes.byref(cfg))
+    cfg.max_iterations = c.max_iterations
+    cfg.cost_tolerance = c.cost_tolerance
+    cfg.parameter_tolerance = c.parameter_tolerance
+    cfg.gradient_tolerance = c.gradient_tolerance
+    cfg.initial_damping = c.initial_damping
+    cfg.min_parallax_sin2 = c.min_parallax_sin2
+    if initial is not None:
+        cfg.flags = _lib.TRI_USE_INITIAL
+        points = _as_device_f64(initial, 3).clone()
+        if points.shape[0] != n:
+            raise ValueError("initial must have one row per point")
+    else:
+        points = torch.empty((n, 3), dtype=torch.float64, device="cuda")
+    status = torch.empty((n,), dtype=torch.uint8, device="cuda")
+    cost = torch.empty((n,), dtype=torch.float64, device="cuda")
+    n_valid = torch.empty((n,), dtype=torch.int32, device="cuda")
+    info = torch.empty((n, 6), dtype=torch.float64, device="cuda") if want_information else None
+    ws_bytes = L.acm_triangulate_workspace_size(n, m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device="cuda")
+    cam = model.acm_camera()
+    _lib.check(L.acm_triangulate(ctypes.byref(cam), pt.shape[0], pt.data_ptr(), n, offs.data_ptr(),
+                                 m, view.data_ptr() if m else None, uv.data_ptr() if m else None,
+                                 ctypes.byref(cfg), points.data_ptr() if n else None,
+                                 status.data_ptr() if n else None, cost.data_ptr() if n else None,
+                                 n_valid.data_ptr() if n else None,
+                                 info.data_ptr() if info is not None and n else None,
+                                 ws.data_ptr(), ws_bytes, _stream_handle()))
+    return TriangulationResult(points, status, cost, n_valid, info)

@@ -1564,6 +1564,307 @@ __global__ __launch_bounds__(kBlock) void k_pose_ne_finish(const double* __restr
     }
 }
 
+// ---------------------------------------------------------- triangulation
+// acm_triangulate: the poses known, the 3-D points unknown -- one 3 x 3
+// problem per point, one lane per point, no cross-point reduction.  A wave's
+// 64 tracks are one contiguous run of the observation arrays: the wave copies
+// that run once, coalesced, into its own LDS region (view index + pixel, 20 B
+// per observation), and the midpoint start and every LM evaluation iterate
+// from there, so HBM sees each observation once per call.  A run longer than
+// kTriStageObs stays in global memory; both cases run the same code on
+// another base pointer (same arithmetic, same order, same bits).  Poses come
+// from LDS when n_views <= kTriPoseLds, else through the cache.  Everything a
+// lane computes depends on its own track, the poses, the camera and the
+// config only: no result depends on the point's place in the batch.
+// The LM is lm_core.hpp's state machine with P = 3 and no bounds (consume /
+// advance), one evaluation site, plus the rule that a trial step with fewer
+// valid observations than the current point is rejected.
+constexpr int kTriStageObs = ACM_TRI_STAGE_OBSERVATIONS;  // per wave; 20 B each
+constexpr int kTriPoseLds = 64;                           // poses staged in LDS up to this many views
+
+struct TriArgs {
+    size_t n_views, n_points, n_obs;
+    const acm_pose* poses;
+    const int64_t* offs;
+    const int32_t* view;
+    const double* uv;
+    double* X;
+    uint8_t* status;
+    double* cost;
+    uint32_t* n_valid;
+    double* info;
+    int max_it, flags;
+    double ctol, ptol, gtol, mu0, sin2;
+};
+
+// A x = b for the symmetric A = [00 01 02 11 12 22] by Cholesky, in
+// lm::cholesky_solve's operation order; false when A is not positive definite
+__device__ __forceinline__ bool tri_chol3(const double* A, const double* b, double* x) {
+    if (!(A[0] > 0.0)) return false;
+    const double l00 = sqrt(A[0]);
+    const double l10 = A[1] / l00;
+    const double s11 = A[3] - l10 * l10;
+    if (!(s11 > 0.0)) return false;
+    const double l11 = sqrt(s11);
+    const double l20 = A[2] / l00;
+    const double l21 = (A[4] - l20 * l10) / l11;
+    const double s22 = A[5] - l20 * l20 - l21 * l21;
+    if (!(s22 > 0.0)) return false;
+    const double l22 = sqrt(s22);
+    const double y0 = b[0] / l00;
+    const double y1 = (b[1] - l10 * y0) / l11;
+    const double y2 = (b[2] - l20 * y0 - l21 * y1) / l22;
+    x[2] = y2 / l22;
+    x[1] = (y1 - l21 * x[2]) / l11;
+    x[0] = (y0 - l10 * x[1] - l20 * x[2]) / l00;
+    return true;
+}
+
+template <class TagT>
+__global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
+    using M = typename TagT::template type<double>;
+    __shared__ double s_uv[kBlock / 64][2 * kTriStageObs];
+    __shared__ int32_t s_view[kBlock / 64][kTriStageObs];
+    __shared__ double s_pose[12 * kTriPoseLds];
+    const Cam<double> c = make_cam<double>(cam);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const bool pose_lds = a.n_views <= (size_t)kTriPoseLds;  // uniform
+    if (pose_lds) {
+        const double* src = reinterpret_cast<const double*>(a.poses);
+        for (size_t k = threadIdx.x; k < 12 * a.n_views; k += kBlock) s_pose[k] = src[k];
+        __syncthreads();
+    }
+    const double* pp = pose_lds ? static_cast<const double*>(s_pose)
+                                : reinterpret_cast<const double*>(a.poses);
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i - (size_t)lane >= a.n_points) return;  // wave-uniform
+    const bool live = i < a.n_points;
+    // the lane's track, clamped into [0, n_obs]: no offset reads out of bounds
+    const long long nobs = (long long)a.n_obs;
+    long long tb = 0, te = 0;
+    if (live) {
+        tb = a.offs[i];
+        te = a.offs[i + 1];
+        tb = tb < 0 ? 0 : (tb > nobs ? nobs : tb);
+        te = te < tb ? tb : (te > nobs ? nobs : te);
+    }
+    // the wave's run [rb, re)
+    long long rb = live ? tb : nobs, re = live ? te : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const long long ob = __shfl_xor(rb, off, 64), oe = __shfl_xor(re, off, 64);
+        rb = ob < rb ? ob : rb;
+        re = oe > re ? oe : re;
+    }
+    const bool staged = re - rb <= (long long)kTriStageObs;  // wave-uniform
+    if (staged) {
+        for (long long k = lane; k < re - rb; k += 64) {
+            s_view[wid][k] = __builtin_nontemporal_load(a.view + rb + k);
+            s_uv[wid][2 * k] = __builtin_nontemporal_load(a.uv + 2 * (rb + k));
+            s_uv[wid][2 * k + 1] = __builtin_nontemporal_load(a.uv + 2 * (rb + k) + 1);
+        }
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    if (!live) return;
+    // observation j of the run is vsrc[j - rb], usrc[2 (j - rb)]
+    const int32_t* vsrc = staged ? static_cast<const int32_t*>(s_view[wid]) : a.view + rb;
+    const double* usrc = staged ? static_cast<const double*>(s_uv[wid]) : a.uv + 2 * rb;
+    const long long jb = tb - rb, je = te - rb;
+
+    auto finish = [&](uint8_t st, double X0, double X1, double X2, double F, uint32_t nv,
+                      const double* A) {
+        a.X[3 * i] = X0;
+        a.X[3 * i + 1] = X1;
+        a.X[3 * i + 2] = X2;
+        a.status[i] = st;
+        if (a.cost) a.cost[i] = F;
+        if (a.n_valid) a.n_valid[i] = nv;
+        if (a.info) {
+#pragma unroll
+            for (int k = 0; k < 6; ++k) a.info[6 * i + k] = A ? A[k] : 0.0;
+        }
+    };
+    const double qnan = __builtin_nan("");
+
+    double x[3];
+    if (a.flags & ACM_TRI_USE_INITIAL) {
+        x[0] = a.X[3 * i];
+        x[1] = a.X[3 * i + 1];
+        x[2] = a.X[3 * i + 2];
+    } else {
+        // midpoint start: A = sum (I - d d^T), b = sum (I - d d^T) c
+        double A00 = 0.0, A01 = 0.0, A02 = 0.0, A11 = 0.0, A12 = 0.0, A22 = 0.0;
+        double b0 = 0.0, b1 = 0.0, b2 = 0.0;
+        uint32_t m = 0;
+        for (long long j = jb; j < je; ++j) {
+            const int32_t vi = vsrc[j];
+            const double u = usrc[2 * j], v = usrc[2 * j + 1];
+            if (!(__builtin_isfinite(u) && __builtin_isfinite(v))) continue;
+            if (vi < 0 || (size_t)vi >= a.n_views) continue;
+            double rx, ry, rz;
+            if (M::unproject(c, u, v, rx, ry, rz) != ST_OK) continue;
+            const double* P = pp + 12 * (size_t)vi;
+            const double d0 = P[0] * rx + P[3] * ry + P[6] * rz;
+            const double d1 = P[1] * rx + P[4] * ry + P[7] * rz;
+            const double d2 = P[2] * rx + P[5] * ry + P[8] * rz;
+            const double c0 = -(P[0] * P[9] + P[3] * P[10] + P[6] * P[11]);
+            const double c1 = -(P[1] * P[9] + P[4] * P[10] + P[7] * P[11]);
+            const double c2 = -(P[2] * P[9] + P[5] * P[10] + P[8] * P[11]);
+            const double dc = d0 * c0 + d1 * c1 + d2 * c2;
+            A00 += 1.0 - d0 * d0;
+            A01 -= d0 * d1;
+            A02 -= d0 * d2;
+            A11 += 1.0 - d1 * d1;
+            A12 -= d1 * d2;
+            A22 += 1.0 - d2 * d2;
+            b0 += c0 - d0 * dc;
+            b1 += c1 - d1 * dc;
+            b2 += c2 - d2 * dc;
+            ++m;
+        }
+        if (m < 2) return finish(ACM_TRI_TOO_FEW_OBSERVATIONS, qnan, qnan, qnan, qnan, m, nullptr);
+        const double k00 = A11 * A22 - A12 * A12, k01 = A02 * A12 - A01 * A22,
+                     k02 = A01 * A12 - A02 * A11, k11 = A00 * A22 - A02 * A02,
+                     k12 = A01 * A02 - A00 * A12, k22 = A00 * A11 - A01 * A01;
+        const double det = A00 * k00 + A01 * k01 + A02 * k02;
+        const double q = (A00 + A11 + A22) * 0.25;
+        if (!(det >= 2.0 * a.sin2 * (q * q * q)))
+            return finish(ACM_TRI_DEGENERATE, qnan, qnan, qnan, qnan, m, nullptr);
+        x[0] = (k00 * b0 + k01 * b1 + k02 * b2) / det;
+        x[1] = (k01 * b0 + k11 * b1 + k12 * b2) / det;
+        x[2] = (k02 * b0 + k12 * b1 + k22 * b2) / det;
+    }
+
+    // LM (lm_core.hpp consume / advance, P = 3): x the accepted point with
+    // its A = J^T J (upper triangle), g = J^T r, F, nv; xn the point under
+    // evaluation, h = xn - x.  term: 0 running, 1 a tolerance, 2 failed.
+    double xn[3] = {x[0], x[1], x[2]}, h[3] = {0.0, 0.0, 0.0};
+    double A[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, g[3] = {0.0, 0.0, 0.0};
+    double F = 0.0, mu = 0.0, nu = 2.0, dmax = 0.0;
+    uint32_t nv = 0;
+    int it = 0, term = 0;
+    bool first = true;
+    for (;;) {
+        double An[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, gn[3] = {0.0, 0.0, 0.0};
+        double F2 = 0.0;
+        uint32_t nvn = 0;
+        for (long long j = jb; j < je; ++j) {
+            const int32_t vi = vsrc[j];
+            const double u = usrc[2 * j], v = usrc[2 * j + 1];
+            if (!(__builtin_isfinite(u) && __builtin_isfinite(v))) continue;
+            if (vi < 0 || (size_t)vi >= a.n_views) continue;
+            const double* P = pp + 12 * (size_t)vi;
+            const double px = P[0] * xn[0] + P[1] * xn[1] + P[2] * xn[2] + P[9];
+            const double py = P[3] * xn[0] + P[4] * xn[1] + P[5] * xn[2] + P[10];
+            const double pz = P[6] * xn[0] + P[7] * xn[1] + P[8] * xn[2] + P[11];
+            double pu, pv, ju[3], jv[3];
+            if (M::template project<false, true, false, true>(c, px, py, pz, pu, pv, ju, jv) != ST_OK)
+                continue;
+            const double r0 = pu - u, r1 = pv - v;
+            double ja[3], jb3[3];  // J = Jpoint(p) R
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                ja[k] = ju[0] * P[k] + ju[1] * P[3 + k] + ju[2] * P[6 + k];
+                jb3[k] = jv[0] * P[k] + jv[1] * P[3 + k] + jv[2] * P[6 + k];
+            }
+            int k = 0;
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                for (int s = r; s < 3; ++s, ++k) An[k] = fma(ja[r], ja[s], fma(jb3[r], jb3[s], An[k]));
+            }
+#pragma unroll
+            for (int r = 0; r < 3; ++r) gn[r] = fma(ja[r], r0, fma(jb3[r], r1, gn[r]));
+            F2 = fma(r0, r0, fma(r1, r1, F2));
+            ++nvn;
+        }
+        const double Fn = 0.5 * F2;
+        bool accept = false;
+        if (first) {
+            first = false;
+            if (nvn < 2) return finish(ACM_TRI_TOO_FEW_OBSERVATIONS, qnan, qnan, qnan, qnan, nvn, nullptr);
+            accept = true;
+            dmax = fmax(An[0], fmax(An[3], An[5]));
+            mu = a.mu0;
+            nu = 2.0;
+            if (a.max_it == 0) term = 1;
+            else if (!__builtin_isfinite(Fn)) term = 2;
+        } else {
+            // predicted reduction L(0) - L(h) = -(g.h + 0.5 h.A.h)
+            const double t0 = A[0] * h[0] + A[1] * h[1] + A[2] * h[2];
+            const double t1 = A[1] * h[0] + A[3] * h[1] + A[4] * h[2];
+            const double t2 = A[2] * h[0] + A[4] * h[1] + A[5] * h[2];
+            const double gh = g[0] * h[0] + g[1] * h[1] + g[2] * h[2];
+            const double hAh = h[0] * t0 + h[1] * t1 + h[2] * t2;
+            const double pred = -(gh + 0.5 * hAh);
+            const double rho = (__builtin_isfinite(Fn) && pred > 0.0 && nvn >= nv) ? (F - Fn) / pred : -1.0;
+            if (rho > 0.0) {
+                accept = true;
+                const double t = 2.0 * rho - 1.0;
+                mu *= fmax(1.0 / 3.0, 1.0 - t * t * t);
+                nu = 2.0;
+            } else {
+                mu *= nu;
+                nu *= 2.0;
+                if (!__builtin_isfinite(mu) || mu > 1e32) term = 2;
+            }
+        }
+        if (accept) {
+            const double dF = F - Fn, Fold = F;
+            const bool trial = it > 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) x[k] = xn[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) A[k] = An[k];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) g[k] = gn[k];
+            F = Fn;
+            nv = nvn;
+            if (term == 0) {
+                if (fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2]))) <= a.gtol) term = 1;
+                else if (trial && dF <= a.ctol * Fold) term = 1;
+            }
+        }
+        // advance to the next point to evaluate, or end
+        bool need = false;
+        while (term == 0 && it < a.max_it) {
+            ++it;
+            double Ad[6] = {A[0], A[1], A[2], A[3], A[4], A[5]};
+            const double floor_d = 1e-12 * fmax(dmax, 1.0);
+            Ad[0] += mu * fmax(A[0], floor_d);
+            Ad[3] += mu * fmax(A[3], floor_d);
+            Ad[5] += mu * fmax(A[5], floor_d);
+            const double mg[3] = {-g[0], -g[1], -g[2]};
+            double hs[3];
+            if (!tri_chol3(Ad, mg, hs)) {
+                mu *= nu;
+                nu *= 2.0;
+                continue;
+            }
+            double hn = 0.0, xnorm = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                xn[k] = x[k] + hs[k];
+                h[k] = xn[k] - x[k];
+                hn += h[k] * h[k];
+                xnorm += x[k] * x[k];
+            }
+            hn = sqrt(hn);
+            xnorm = sqrt(xnorm);
+            if (hn <= a.ptol * (xnorm + a.ptol)) {
+                term = 1;
+                break;
+            }
+            need = true;
+            break;
+        }
+        if (!need) break;
+    }
+    finish(term == 1 ? ACM_TRI_OK : ACM_TRI_NOT_CONVERGED, x[0], x[1], x[2], F, nv, A);
+}
+
 // ----------------------------------------------------- reprojection stats
 // One streaming pass.  The variance is not a second pass over the errors
 // (error_metrics.rs:92 sums (e - mean)^2 after the mean): each lane keeps
@@ -5409,6 +5710,70 @@ ACM_API int acm_pose_normal_equations(const acm_camera* cam, const acm_pose* pos
                            points_2d_obs, parts);
         hipLaunchKernelGGL(k_pose_ne_finish, dim3(kPoseK), dim3(kBlock), 0, s, parts, nb, result);
         return check_launch("acm_pose_normal_equations");
+    });
+}
+
+ACM_API void acm_triangulate_default_config(acm_triangulate_config* cfg) {
+    if (!cfg) return;
+    cfg->max_iterations = 20;
+    cfg->flags = 0;
+    cfg->cost_tolerance = 1e-6;
+    cfg->parameter_tolerance = 1e-8;
+    cfg->gradient_tolerance = 1e-6;
+    cfg->initial_damping = 1e-4;
+    cfg->min_parallax_sin2 = 1e-8;
+}
+
+// The kernel keeps everything in registers and LDS: the workspace is a
+// reserved 64 bytes, whatever the shape.
+ACM_API size_t acm_triangulate_workspace_size(size_t, size_t) { return 64; }
+
+ACM_API int acm_triangulate(const acm_camera* cam, size_t n_views, const acm_pose* poses,
+                            size_t n_points, const int64_t* track_offsets, size_t n_observations,
+                            const int32_t* obs_view, const double* obs_uv,
+                            const acm_triangulate_config* cfg, double* points_world,
+                            uint8_t* status, double* cost, uint32_t* n_valid, double* information,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
+    if (cfg->max_iterations < 0 || (cfg->flags & ~ACM_TRI_USE_INITIAL))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "negative max_iterations or unknown flag bits");
+    if (n_points == 0) return ACM_SUCCESS;
+    if (!poses || !track_offsets || !points_world || !status ||
+        (n_observations && (!obs_view || !obs_uv)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace || workspace_bytes < acm_triangulate_workspace_size(n_points, n_observations))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "triangulation workspace too small");
+    if (n_points > (size_t)0x7fffffff * kBlock)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many points for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_model(cam->model, [&](auto tag) -> int {
+        using TagT = decltype(tag);
+        TriArgs a;
+        a.n_views = n_views;
+        a.n_points = n_points;
+        a.n_obs = n_observations;
+        a.poses = poses;
+        a.offs = track_offsets;
+        a.view = obs_view;
+        a.uv = obs_uv;
+        a.X = points_world;
+        a.status = status;
+        a.cost = cost;
+        a.n_valid = n_valid;
+        a.info = information;
+        a.max_it = cfg->max_iterations;
+        a.flags = cfg->flags;
+        a.ctol = cfg->cost_tolerance;
+        a.ptol = cfg->parameter_tolerance;
+        a.gtol = cfg->gradient_tolerance;
+        a.mu0 = cfg->initial_damping;
+        a.sin2 = cfg->min_parallax_sin2;
+        const unsigned nb = (unsigned)((n_points + kBlock - 1) / kBlock);
+        hipLaunchKernelGGL(k_triangulate<TagT>, dim3(nb), dim3(kBlock), 0, s,
+                           prep(*cam, false, true), a);
+        return check_launch("acm_triangulate");
     });
 }
 

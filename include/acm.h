@@ -486,6 +486,104 @@ ACM_API int acm_pose_optimize(const acm_camera *cam, acm_pose *pose, size_t n,
                               acm_lm_summary *summary, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* Batched multi-view triangulation: the dual of pose refinement -- the
+ * poses (world -> camera, p_cam = R X + t) are known, the unknowns are the
+ * 3-D points, one independent 3 x 3 problem per point.  One camera
+ * (intrinsics) serves all views; a rig with different intrinsics per view is
+ * out of scope.
+ *
+ * Tracks are CSR: point i owns observations track_offsets[i] ..
+ * track_offsets[i + 1] - 1, in that order (track_offsets: n_points + 1
+ * entries, non-decreasing, [0] = 0, the last <= n_observations; entries
+ * outside [0, n_observations] are clamped, so no offset can make the call
+ * read out of bounds).  Observation j is the pixel obs_uv[2 j], obs_uv[2 j + 1]
+ * seen through poses[obs_view[j]].
+ *
+ * Midpoint start (skipped with ACM_TRI_USE_INITIAL, which starts from
+ * points_world as given).  An observation is usable iff its pixel is finite,
+ * its view index lies in [0, n_views) and the unprojection of the pixel
+ * (acm_unproject's default numerics) is Ok; anything else is skipped -- an
+ * out-of-range view index is never dereferenced and is no error of the call.
+ * Per usable observation d = R^T ray, c = -R^T t; A = sum (I - d d^T),
+ * b = sum (I - d d^T) c, in track order.  Fewer than 2 usable observations:
+ * ACM_TRI_TOO_FEW_OBSERVATIONS.  det(A) < 2 min_parallax_sin2 (tr(A) / 4)^3:
+ * ACM_TRI_DEGENERATE (for two rays at angle phi this reads sin^2 phi <
+ * min_parallax_sin2).  Otherwise X0 = A^-1 b.  (UCM's start inherits the
+ * reference's 1 - r^2 unprojection quirk; the refinement removes
+ * it.)
+ *
+ * Refinement: minimise sum ||project(R X + t) - uv||^2 (the fast projection
+ * of acm_pose_normal_equations) over the observations whose pixel is finite,
+ * whose view is in range and whose projection at the current X is Ok; their
+ * count is n_valid.  Per observation J = Jpoint(p) R (2 x 3); sums in track
+ * order.  The loop is acm_lm_optimize's state machine with P = 3 and no
+ * bounds (Marquardt-scaled damping with the same floor, Nielsen update, a
+ * failed Cholesky raises the damping, the same three tolerances, damping >
+ * 1e32 fails, one evaluation per trial step), plus one rule: a trial step
+ * whose n_valid is smaller than the current one's is rejected (a two-view
+ * point must not lower its cost by losing an observation).  Fewer than 2
+ * valid observations at the start point: ACM_TRI_TOO_FEW_OBSERVATIONS.  A
+ * tolerance ends the loop: ACM_TRI_OK.  The iteration limit or a failure:
+ * ACM_TRI_NOT_CONVERGED, with the best accepted X written.  max_iterations
+ * = 0: the start point, ACM_TRI_OK, cost / n_valid / information evaluated
+ * there.
+ *
+ * Outputs per point: points_world (3 f64, AoS; in/out with
+ * ACM_TRI_USE_INITIAL), status (acm_tri_status), and when non-NULL cost
+ * (0.5 sum ||r||^2 at the returned X), n_valid, information (the upper
+ * triangle of the undamped J^T J at the returned X, row by row: xx xy xz yy
+ * yz zz).  ACM_TRI_TOO_FEW_OBSERVATIONS and ACM_TRI_DEGENERATE write X = NaN,
+ * cost = NaN, information = 0 and n_valid = the count that decided (usable
+ * observations of the start, or valid ones at the start point).
+ *
+ * A point's outputs depend only on its own observation list in order, the
+ * poses, the camera and the config -- not on n_points, its index, its
+ * neighbours or the launch: the same track gives the same bits anywhere in
+ * any batch.  One lane per point; each wave stages the contiguous run of its
+ * 64 tracks' observations in LDS once (20 B each) when the run holds at most
+ * ACM_TRI_STAGE_OBSERVATIONS of them, and reads global memory per evaluation
+ * otherwise (the same arithmetic in the same order).
+ *
+ * Errors: NULL cam / poses / track_offsets / cfg / points_world / status, or
+ * NULL obs_view / obs_uv with n_observations > 0, negative max_iterations or
+ * unknown flag bits: ACM_ERR_INVALID_ARGUMENT; a bad model:
+ * ACM_ERR_INVALID_MODEL; a NULL or short workspace (device,
+ * acm_triangulate_workspace_size bytes): ACM_ERR_WORKSPACE_TOO_SMALL.
+ * n_points = 0 is valid and touches nothing.  Stream-ordered, no allocation,
+ * reentrant. */
+typedef enum acm_tri_status {
+    ACM_TRI_OK = 0,
+    ACM_TRI_TOO_FEW_OBSERVATIONS = 1, /* fewer than 2 usable observations */
+    ACM_TRI_DEGENERATE = 2,           /* rays (nearly) parallel: no depth */
+    ACM_TRI_NOT_CONVERGED = 3         /* iteration limit or damping overflow; X still written */
+} acm_tri_status;
+
+enum { ACM_TRI_USE_INITIAL = 1 };     /* start from points_world as given, skip the midpoint start */
+
+/* observations a wave stages in LDS (20 B each); a longer run is read from
+ * global memory at every evaluation */
+#define ACM_TRI_STAGE_OBSERVATIONS 512
+
+typedef struct acm_triangulate_config {
+    int32_t max_iterations;      /* per point; 0 = midpoint start only.  default 20 */
+    int32_t flags;               /* 0 or ACM_TRI_USE_INITIAL */
+    double cost_tolerance;       /* defaults of acm_lm_default_config: 1e-6 */
+    double parameter_tolerance;  /* 1e-8 */
+    double gradient_tolerance;   /* 1e-6 */
+    double initial_damping;      /* 1e-4 */
+    double min_parallax_sin2;    /* degeneracy threshold, above.  default 1e-8 */
+} acm_triangulate_config;
+
+ACM_API void acm_triangulate_default_config(acm_triangulate_config *cfg);
+ACM_API size_t acm_triangulate_workspace_size(size_t n_points, size_t n_observations);
+ACM_API int acm_triangulate(const acm_camera *cam, size_t n_views, const acm_pose *poses,
+                            size_t n_points, const int64_t *track_offsets,
+                            size_t n_observations, const int32_t *obs_view,
+                            const double *obs_uv, const acm_triangulate_config *cfg,
+                            double *points_world, uint8_t *status, double *cost,
+                            uint32_t *n_valid, double *information, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* (r06) The sharded conversion's collectives.  One
  * process per GPU, each holding a shard of the correspondences; both
  * collectives are stream-ordered on device f64 buffers:

@@ -12,6 +12,9 @@
 //                      trivial function of the inputs instead of the camera
 //                      model -- the same bytes, in the same instruction shape,
 //                      with (almost) no VALU work.
+//   acm_probe_triangulate: acm_triangulate's traffic (8 + 20 L B read, 25 B
+//                      written per point) with its LDS staging and no math;
+//                      driven by tools/bench_triangulate.py.
 //
 // Built by tools/Makefile (hipcc --offload-arch=gfx950); driven by
 // tools/hbm_ceiling.py.
@@ -397,5 +400,57 @@ extern "C" int acm_probe_sqrt_rn(const double* a, size_t n, unsigned long long* 
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_sqrt_rn_check, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, a, n, mismatches, first);
+    return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+// ---------------------------------------------------------------------------
+// acm_probe_triangulate: the algorithmic traffic of acm_triangulate with no
+// camera math -- per point 8 B of track offsets and 20 B per observation
+// (4-B view index + 16-B pixel) read, 24 B of point + 1 B of status written
+// (8 + 20 L in, 25 out).  One lane per point; as k_triangulate, each wave
+// copies the contiguous run of its 64 tracks into LDS with coalesced loads
+// and every lane then sums its own observations from there.  offsets must be
+// non-decreasing with offsets[n] <= the observation count, and a wave's run
+// at most 512 observations (tools/bench_triangulate.py's tracks are).
+__global__ __launch_bounds__(256) void k_tri_mimic(size_t n, const long long* __restrict__ offs,
+                                                   const int* __restrict__ view,
+                                                   const double* __restrict__ uv,
+                                                   double* __restrict__ X,
+                                                   uint8_t* __restrict__ st) {
+    __shared__ double s_uv[4][1024];
+    __shared__ int s_view[4][512];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t w0 = i - lane;
+    if (w0 >= n) return;
+    const size_t wl = w0 + 64 < n ? w0 + 64 : n;
+    const long long rb = offs[w0], re = offs[wl];
+    if (re - rb > 512) return;
+    for (long long k = lane; k < re - rb; k += 64) {
+        s_view[wid][k] = __builtin_nontemporal_load(view + rb + k);
+        s_uv[wid][2 * k] = __builtin_nontemporal_load(uv + 2 * (rb + k));
+        s_uv[wid][2 * k + 1] = __builtin_nontemporal_load(uv + 2 * (rb + k) + 1);
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (i >= n) return;
+    double a = 0.0, b = 0.0, c = 0.0;
+    for (long long j = offs[i] - rb; j < offs[i + 1] - rb; ++j) {
+        a += s_uv[wid][2 * j];
+        b += s_uv[wid][2 * j + 1];
+        c += (double)s_view[wid][j];
+    }
+    X[3 * i] = a;
+    X[3 * i + 1] = b;
+    X[3 * i + 2] = c;
+    st[i] = (uint8_t)(offs[i + 1] - offs[i]);
+}
+
+extern "C" int acm_probe_triangulate(size_t n, const long long* offs, const int* view,
+                                     const double* uv, double* X, uint8_t* st, void* stream) {
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(k_tri_mimic, dim3(blocks(n)), dim3(256), 0, (hipStream_t)stream, n, offs,
+                       view, uv, X, st);
     return hipGetLastError() == hipSuccess ? 0 : 1;
 }
