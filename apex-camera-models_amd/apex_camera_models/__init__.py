@@ -15,13 +15,15 @@ from .camera import (CameraModel, CameraModelError, DoubleSphereModel, EucmModel
                      Resolution, UcmModel)
 from .util import (ImageQualityMetrics, calculate_psnr, calculate_ssim,  # noqa: E402
                    compute_image_quality_metrics)
-from .optimizer import (Pose, TriangulationConfig, TriangulationResult, refine_pose,  # noqa: E402
-                        tracks_from_dense, triangulate)
+from .optimizer import (Pose, PoseBatchConfig, PoseBatchResult, TriangulationConfig,  # noqa: E402
+                        TriangulationResult, alternate_bundle_adjustment, refine_pose,
+                        refine_poses, tracks_by_view, tracks_from_dense, triangulate)
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
     "EucmModel", "FovModel", "Intrinsics", "KannalaBrandtModel", "PinholeModel", "RadTanModel",
     "Resolution", "UcmModel", "ImageQualityMetrics", "calculate_psnr", "calculate_ssim",
     "compute_image_quality_metrics", "Pose", "refine_pose", "triangulate", "tracks_from_dense",
-    "TriangulationConfig", "TriangulationResult",
+    "TriangulationConfig", "TriangulationResult", "PoseBatchConfig", "PoseBatchResult",
+    "refine_poses", "tracks_by_view", "alternate_bundle_adjustment",
 ]

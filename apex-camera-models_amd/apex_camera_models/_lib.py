@@ -114,6 +114,23 @@ TRI_USE_INITIAL = 1
 TRI_STAGE_OBSERVATIONS = 512
 
 
+class PoseBatchConfig(ctypes.Structure):
+    """acm_pose_batch_config (include/acm.h)."""
+    _fields_ = [
+        ("max_iterations", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("cost_tolerance", ctypes.c_double),
+        ("parameter_tolerance", ctypes.c_double),
+        ("gradient_tolerance", ctypes.c_double),
+        ("initial_damping", ctypes.c_double),
+    ]
+
+
+# acm_pose_status / the per-view LDS staging budget (include/acm.h)
+POSE_OK, POSE_TOO_FEW_OBSERVATIONS, POSE_NOT_CONVERGED = 0, 1, 2
+POSE_BATCH_STAGE_OBSERVATIONS = 1024
+
+
 class CellGrid(ctypes.Structure):
     """acm_cell_grid (include/acm.h, r06): the grid of a cell-form sample."""
     _fields_ = [
@@ -196,6 +213,9 @@ EXPORTED_SYMBOLS = (
     "acm_triangulate_default_config",
     "acm_triangulate_workspace_size",
     "acm_triangulate",
+    "acm_pose_optimize_batch_default_config",
+    "acm_pose_optimize_batch_workspace_size",
+    "acm_pose_optimize_batch",
     "acm_sample_points_cells",
     "acm_rccl_available",
     "acm_rccl_unique_id",
@@ -381,6 +401,14 @@ def load():
     L.acm_triangulate.argtypes = [cam_p, sz, vp, sz, vp, sz, vp, vp, tri_p, vp, vp, vp, vp, vp,
                                   vp, sz, vp]
     L.acm_triangulate.restype = i
+    pb_p = ctypes.POINTER(PoseBatchConfig)
+    L.acm_pose_optimize_batch_default_config.argtypes = [pb_p]
+    L.acm_pose_optimize_batch_default_config.restype = None
+    L.acm_pose_optimize_batch_workspace_size.argtypes = [sz, sz]
+    L.acm_pose_optimize_batch_workspace_size.restype = sz
+    L.acm_pose_optimize_batch.argtypes = [cam_p, sz, vp, sz, vp, vp, sz, vp, vp, pb_p, vp, vp, vp,
+                                          vp, vp, vp, sz, vp]
+    L.acm_pose_optimize_batch.restype = i
     L.acm_sample_points_cells.argtypes = [cam_p, sz, sz, sz, i, vp, vp, vp, vp, vp, sz, vp]
     L.acm_sample_points_cells.restype = i
     L.acm_reprojection_error_cells.argtypes = [cam_p, sz, vp, i, vp, grid_p, vp, vp, vp, sz, vp]

@@ -340,3 +340,134 @@ def triangulate(model: CameraModel, poses, track_offsets, obs_view, obs_uv, init
                                  info.data_ptr() if info is not None and n else None,
                                  ws.data_ptr(), ws_bytes, _stream_handle()))
     return TriangulationResult(points, status, cost, n_valid, info)
+
+
+# ------------------------------------------------- batched pose refinement
+@dataclass
+class PoseBatchConfig:
+    """acm_pose_batch_config; the defaults are acm_pose_optimize_batch_default_config's."""
+    max_iterations: int = 20
+    cost_tolerance: float = 1e-6
+    parameter_tolerance: float = 1e-8
+    gradient_tolerance: float = 1e-6
+    initial_damping: float = 1e-4
+
+
+@dataclass
+class PoseBatchResult:
+    """Device tensors, one row per view: poses (K, 12) f64 (R row-major, then
+    t), status (K,) u8 (_lib.POSE_OK / POSE_TOO_FEW_OBSERVATIONS /
+    POSE_NOT_CONVERGED), cost (K,) f64, n_valid (K,) i32, iterations (K,) i32,
+    information (K, 21) f64 -- the upper triangle of J^T J, row by row -- or
+    None."""
+    poses: torch.Tensor
+    status: torch.Tensor
+    cost: torch.Tensor
+    n_valid: torch.Tensor
+    iterations: torch.Tensor
+    information: Optional[torch.Tensor]
+
+
+def tracks_by_view(track_offsets, obs_view, obs_uv, n_views):
+    """The view-major CSR of point-major tracks (track_offsets (N + 1,),
+    obs_view (M,), obs_uv (M, 2), as acm_triangulate takes them): returns
+    (view_offsets (K + 1,) int64, obs_point (M',) int32, obs_uv (M', 2) f64) on
+    the inputs' device.  A stable sort on the view index, so each view's
+    observations are in ascending point order (and in track order within a
+    point); observations whose view index is outside [0, n_views) are
+    dropped."""
+    offs = torch.as_tensor(track_offsets).to(torch.int64)
+    dev = offs.device
+    view = torch.as_tensor(obs_view).to(device=dev, dtype=torch.int64)
+    uv = torch.as_tensor(obs_uv).to(device=dev, dtype=torch.float64).reshape(-1, 2)
+    m = view.shape[0]
+    n = offs.shape[0] - 1
+    if n < 0 or uv.shape[0] != m:
+        raise ValueError("track_offsets needs N + 1 entries; obs_view and obs_uv one row per observation")
+    k = int(n_views)
+    # the point of observation j: the track whose [begin, end) holds j
+    j = torch.arange(m, dtype=torch.int64, device=dev)
+    point = torch.searchsorted(offs[1:].contiguous(), j, right=True)
+    keep = (view >= 0) & (view < k) & (point < n) & (j >= offs[0])
+    view, point, uv = view[keep], point[keep], uv[keep]
+    order = torch.sort(view, stable=True).indices
+    view_offsets = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+    if k:
+        view_offsets[1:] = torch.cumsum(torch.bincount(view, minlength=k)[:k], dim=0)
+    return view_offsets, point[order].to(torch.int32).contiguous(), uv[order].contiguous()
+
+
+def refine_poses(model: CameraModel, poses, points_world, view_offsets, obs_point, obs_uv,
+                 config: Optional[PoseBatchConfig] = None,
+                 want_information: bool = False) -> PoseBatchResult:
+    """Batched 6-DoF pose refinement (acm_pose_optimize_batch): every view's
+    pose from known world points, one Levenberg-Marquardt per view, all in one
+    launch.  poses: a sequence of Pose or a (K, 12) tensor (not modified);
+    points_world (N, 3); view_offsets (K + 1,) int64, obs_point (M,) int32,
+    obs_uv (M, 2) f64: the observations by view (tracks_by_view builds them
+    from tracks).  Non-finite points (triangulate's failures) are skipped."""
+    L = _lib.load()
+    pt = _poses_tensor(poses).clone()
+    pw = _as_device_f64(points_world, 3)
+    offs = torch.as_tensor(view_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    idx = torch.as_tensor(obs_point).to(device="cuda", dtype=torch.int32).contiguous()
+    uv = _as_device_f64(obs_uv, 2)
+    k, n, m = pt.shape[0], pw.shape[0], idx.shape[0]
+    if offs.shape[0] != k + 1 or uv.shape[0] != m:
+        raise ValueError("view_offsets needs K + 1 entries; obs_point and obs_uv one row per observation")
+    c = config or PoseBatchConfig()
+    cfg = _lib.PoseBatchConfig()
+    L.acm_pose_optimize_batch_default_config(ctypes.byref(cfg))
+    cfg.max_iterations = c.max_iterations
+    cfg.cost_tolerance = c.cost_tolerance
+    cfg.parameter_tolerance = c.parameter_tolerance
+    cfg.gradient_tolerance = c.gradient_tolerance
+    cfg.initial_damping = c.initial_damping
+    status = torch.empty((k,), dtype=torch.uint8, device="cuda")
+    cost = torch.empty((k,), dtype=torch.float64, device="cuda")
+    n_valid = torch.empty((k,), dtype=torch.int32, device="cuda")
+    iters = torch.empty((k,), dtype=torch.int32, device="cuda")
+    info = torch.empty((k, 21), dtype=torch.float64, device="cuda") if want_information else None
+    ws_bytes = L.acm_pose_optimize_batch_workspace_size(k, m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device="cuda")
+    cam = model.acm_camera()
+    _lib.check(L.acm_pose_optimize_batch(
+        ctypes.byref(cam), k, pt.data_ptr() if k else None, n, pw.data_ptr() if n else None,
+        offs.data_ptr(), m, idx.data_ptr() if m else None, uv.data_ptr() if m else None,
+        ctypes.byref(cfg), status.data_ptr() if k else None, cost.data_ptr() if k else None,
+        n_valid.data_ptr() if k else None, iters.data_ptr() if k else None,
+        info.data_ptr() if info is not None and k else None, ws.data_ptr(), ws_bytes,
+        _stream_handle()))
+    return PoseBatchResult(pt, status, cost, n_valid, iters, info)
+
+
+def alternate_bundle_adjustment(model: CameraModel, poses, track_offsets, obs_view, obs_uv,
+                                sweeps: int, fixed_views: Sequence[int] = (0,),
+                                initial_points=None):
+    """Alternating bundle adjustment from the two batched launches:
+    triangulate, then `sweeps` x (refine_poses, triangulate from the previous
+    points), all on the device with no per-view Python.  The poses of
+    fixed_views (the gauge) are restored after every pose step, and the cost
+    of that step is evaluated at the restored poses (max_iterations = 0).  A
+    point that triangulate could not solve stays NaN and is skipped by both
+    halves.  Returns (poses (K, 12), the last TriangulationResult, costs) with
+    costs the total cost (0-d device tensors; the NaN costs of unsolved points
+    / views left out) after every half step: 1 + 2 sweeps entries."""
+    pt = _poses_tensor(poses).clone()
+    start = pt.clone()
+    fixed = torch.as_tensor(list(fixed_views), dtype=torch.int64, device=pt.device)
+    offs = torch.as_tensor(track_offsets).to(device="cuda", dtype=torch.int64)
+    view = torch.as_tensor(obs_view).to(device="cuda", dtype=torch.int32)
+    uv = _as_device_f64(obs_uv, 2)
+    view_offsets, obs_point, view_uv = tracks_by_view(offs, view, uv, pt.shape[0])
+    evaluate = PoseBatchConfig(max_iterations=0)
+    tri = triangulate(model, pt, offs, view, uv, initial=initial_points)
+    costs = [torch.nansum(tri.cost)]
+    for _ in range(int(sweeps)):
+        pt = refine_poses(model, pt, tri.points, view_offsets, obs_point, view_uv).poses
+        pt[fixed] = start[fixed]
+        at = refine_poses(model, pt, tri.points, view_offsets, obs_point, view_uv, evaluate)
+        costs.append(torch.nansum(at.cost))
+        tri = triangulate(model, pt, offs, view, uv, initial=tri.points)
+        costs.append(torch.nansum(tri.cost))
+    return pt, tri, costs

@@ -1865,6 +1865,412 @@ __global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
     finish(term == 1 ? ACM_TRI_OK : ACM_TRI_NOT_CONVERGED, x[0], x[1], x[2], F, nv, A);
 }
 
+// ------------------------------------------------- batched pose refinement
+// acm_pose_optimize_batch: the points known, the poses unknown -- one 6 x 6
+// problem per view, one workgroup per view, the whole LM on the device.  The
+// view's observations (pixel + gathered world point, 40 B) are staged once in
+// LDS when there are at most kPoseStageObs of them; a longer view gathers
+// from global memory at every evaluation (same arithmetic, same order, same
+// bits).  Lane l sums observations l, l + 256, ... (k_pose_normal_eq's 29
+// sums and per-observation arithmetic); block_sum_lds reduces them in
+// block_sum_store's grouping and leaves the totals in LDS; every lane then
+// runs the same LM step (lm_core.hpp consume / advance, P = 6, local
+// coordinates as acm_pose_optimize) on the same 29 numbers, so all control
+// flow after the reduction is workgroup-uniform and no decision is broadcast.
+// Everything a workgroup computes depends on its own view only.
+constexpr int kPoseStageObs = ACM_POSE_BATCH_STAGE_OBSERVATIONS;  // per view; 40 B each
+
+struct PoseBatchArgs {
+    size_t n_points, n_obs;
+    acm_pose* poses;
+    const double* X;
+    const int64_t* offs;
+    const int32_t* pt;
+    const double* uv;
+    uint8_t* status;
+    double* cost;
+    uint32_t* n_valid;
+    int32_t* iters;
+    double* info;
+    int max_it;
+    double ctol, ptol, gtol, mu0;
+};
+
+// block_sum_store's reduction (the wave reduce-scatter, then the four waves
+// in order) with LDS as the destination: tot[0..K) holds the workgroup sums
+// for every lane when it returns.  Two barriers; safe to call again at once.
+template <int K>
+__device__ __forceinline__ void block_sum_lds(const double (&acc)[K], double (&sm)[kBlock / 64][K],
+                                              double (&tot)[K]) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    constexpr int KP = pow2_at_least(K) < 64 ? pow2_at_least(K) : 64;
+    static_assert(K <= 64, "reduce-scatter over one wave");
+    constexpr int m = log2_exact(KP);
+    double v[KP];
+#pragma unroll
+    for (int k = 0; k < KP; ++k) v[k] = k < K ? acc[k] : 0.0;
+#pragma unroll
+    for (int st = 0; st < m; ++st) {
+        const int h = KP >> (st + 1), o = 32 >> st;
+        const bool up = (lane & o) != 0;
+#pragma unroll
+        for (int j = 0; j < h; ++j) {
+            const double send = up ? v[j] : v[j + h];
+            const double keep = up ? v[j + h] : v[j];
+            v[j] = keep + __shfl_xor(send, o, 64);
+        }
+    }
+    double t = v[0];
+#pragma unroll
+    for (int o = (32 >> m); o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+    const int idx = lane >> (6 - m);
+    if ((lane & ((1 << (6 - m)) - 1)) == 0 && idx < K) sm[wid][idx] = t;
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) s += sm[w][threadIdx.x];
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+}
+
+// index of (r, q), r <= q, in the row-by-row upper triangle of a 6 x 6
+__host__ __device__ constexpr int pose_ut(int r, int q) {
+    return r <= q ? r * 6 - r * (r - 1) / 2 + (q - r) : q * 6 - q * (q - 1) / 2 + (r - q);
+}
+
+// A x = b for the symmetric 6 x 6 A (upper triangle, 21) by Cholesky, in
+// lm::cholesky_solve's operation order, every index a compile-time constant;
+// false when A is not positive definite
+__device__ __forceinline__ bool pose_chol6(const double (&A)[21], const double (&b)[6],
+                                           double (&x)[6]) {
+    double L[21];  // lower triangle, (i, j) at pose_ut(j, i)
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double s = A[pose_ut(j, i)];
+#pragma unroll
+            for (int q = 0; q < j; ++q) s -= L[pose_ut(q, i)] * L[pose_ut(q, j)];
+            if (i == j) {
+                if (!(s > 0.0)) return false;
+                L[pose_ut(i, i)] = sqrt(s);
+            } else {
+                L[pose_ut(j, i)] = s / L[pose_ut(j, j)];
+            }
+        }
+    }
+    double y[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double s = b[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) s -= L[pose_ut(q, i)] * y[q];
+        y[i] = s / L[pose_ut(i, i)];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int q = i + 1; q < 6; ++q) s -= L[pose_ut(i, q)] * x[q];
+        x[i] = s / L[pose_ut(i, i)];
+    }
+    return true;
+}
+
+// acm_pose_retract's formulas in double: out = (Exp(phi) R, Exp(phi) t + rho)
+__device__ __forceinline__ void pose_retract_dev(const double (&P)[12], const double (&d)[6],
+                                                 double (&out)[12]) {
+    const double px = d[3], py = d[4], pz = d[5];
+    const double t2 = px * px + py * py + pz * pz;
+    double A, B;
+    if (t2 < 1e-6) {
+        A = 1.0 - t2 / 6.0 + t2 * t2 / 120.0;
+        B = 0.5 - t2 / 24.0 + t2 * t2 / 720.0;
+    } else {
+        const double th = sqrt(t2), hf = 0.5 * th;
+        const double sh = sin(hf) / hf;
+        A = sin(th) / th;
+        B = 0.5 * sh * sh;
+    }
+    // K^2 = phi phi^T - th^2 I
+    const double E[9] = {1.0 - B * (py * py + pz * pz), B * px * py - A * pz, B * px * pz + A * py,
+                         B * px * py + A * pz, 1.0 - B * (px * px + pz * pz), B * py * pz - A * px,
+                         B * px * pz - A * py, B * py * pz + A * px, 1.0 - B * (px * px + py * py)};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            out[3 * i + j] = E[3 * i] * P[j] + E[3 * i + 1] * P[3 + j] + E[3 * i + 2] * P[6 + j];
+        out[9 + i] = E[3 * i] * P[9] + E[3 * i + 1] * P[10] + E[3 * i + 2] * P[11] + d[i];
+    }
+}
+
+// the LM state of a view in LDS (doubles)
+enum : int {
+    kStCur = 0, kStX = 12, kStXn = 18, kStH = 24, kStA = 30, kStG = 51, kStF = 57, kStNv = 58,
+    kStMu = 59, kStNu = 60, kStDmax = 61, kStSize = 62
+};
+
+template <class TagT>
+__global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs a) {
+    using M = typename TagT::template type<double>;
+    __shared__ double s_obs[5][kPoseStageObs];  // x, y, z, u, v of the staged observations
+    __shared__ double s_part[kBlock / 64][kPoseK];
+    __shared__ double s_tot[kPoseK];
+    __shared__ double s_st[2][kStSize];
+    const Cam<double> c = make_cam<double>(cam);
+    const size_t view = blockIdx.x;
+    // the view's observations, clamped into [0, n_obs]: no offset reads out of bounds
+    const long long nobs = (long long)a.n_obs;
+    long long ob = a.offs[view], oe = a.offs[view + 1];
+    ob = ob < 0 ? 0 : (ob > nobs ? nobs : ob);
+    oe = oe < ob ? ob : (oe > nobs ? nobs : oe);
+    const long long cnt = oe - ob;
+    const bool staged = cnt <= (long long)kPoseStageObs;  // workgroup-uniform
+    const double qnan = __builtin_nan("");
+
+    // observation j of the view from global memory: the pixel and the gathered
+    // world point, the point NaN when its index is out of range (never
+    // dereferenced) -- a non-finite point or pixel is skipped by accumulate
+    auto gather = [&](long long j, double& X, double& Y, double& Z, double& u, double& v) {
+        const int32_t pi = a.pt[ob + j];
+        u = a.uv[2 * (ob + j)];
+        v = a.uv[2 * (ob + j) + 1];
+        X = Y = Z = qnan;
+        if (pi >= 0 && (size_t)pi < a.n_points) {
+            X = a.X[3 * (size_t)pi];
+            Y = a.X[3 * (size_t)pi + 1];
+            Z = a.X[3 * (size_t)pi + 2];
+        }
+        if (!(__builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z))) X = Y = Z = qnan;
+    };
+    if (staged) {
+        for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+            double X, Y, Z, u, v;
+            gather(j, X, Y, Z, u, v);
+            s_obs[0][j] = X;
+            s_obs[1][j] = Y;
+            s_obs[2][j] = Z;
+            s_obs[3][j] = u;
+            s_obs[4][j] = v;
+        }
+        __syncthreads();
+    }
+
+    double ev[12];  // the pose under evaluation: the start pose, then retract(accepted, h)
+    {
+        const double* src = reinterpret_cast<const double*>(a.poses + view);
+#pragma unroll
+        for (int k = 0; k < 12; ++k) ev[k] = src[k];
+    }
+
+    // LM state (lm_core.hpp, P = 6): cur the accepted pose, x the accepted
+    // steps summed from 0, A = J^T J (upper triangle), g = J^T r, F, nv at
+    // the accepted pose; xn = x + h the step under evaluation.  Between two
+    // evaluations the state rests in LDS (it is the same in every lane), so
+    // the sums and the projection have the registers to themselves: a step
+    // reads s_st[par], lane 0 writes the next state to s_st[par ^ 1] (the two
+    // barriers of the next reduction lie between that write and its reads,
+    // and between a buffer's last read and its next write).  term: 0
+    // running, 1 a tolerance, 2 failed.
+    int it = 0, term = 0, par = 0;
+    bool first = true;
+    for (;;) {
+        double acc[kPoseK];
+#pragma unroll
+        for (int k = 0; k < kPoseK; ++k) acc[k] = 0.0;
+        for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+            double X, Y, Z, ou, ov;
+            if (staged) {
+                X = s_obs[0][j];
+                Y = s_obs[1][j];
+                Z = s_obs[2][j];
+                ou = s_obs[3][j];
+                ov = s_obs[4][j];
+            } else {
+                gather(j, X, Y, Z, ou, ov);
+            }
+            if (!(__builtin_isfinite(ou) && __builtin_isfinite(ov) && __builtin_isfinite(X))) continue;
+            const double px = ev[0] * X + ev[1] * Y + ev[2] * Z + ev[9];
+            const double py = ev[3] * X + ev[4] * Y + ev[5] * Z + ev[10];
+            const double pz = ev[6] * X + ev[7] * Y + ev[8] * Z + ev[11];
+            double u, v, ju[3], jv[3];
+            if (M::template project<false, true, false, true>(c, px, py, pz, u, v, ju, jv) != ST_OK)
+                continue;
+            const double r0 = u - ou, r1 = v - ov;
+            const double ja[6] = {ju[0], ju[1], ju[2], py * ju[2] - pz * ju[1],
+                                  pz * ju[0] - px * ju[2], px * ju[1] - py * ju[0]};
+            const double jb[6] = {jv[0], jv[1], jv[2], py * jv[2] - pz * jv[1],
+                                  pz * jv[0] - px * jv[2], px * jv[1] - py * jv[0]};
+            int k = 0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+#pragma unroll
+                for (int q = r; q < 6; ++q, ++k) acc[k] = fma(ja[r], ja[q], fma(jb[r], jb[q], acc[k]));
+            }
+#pragma unroll
+            for (int r = 0; r < 6; ++r) acc[21 + r] = fma(ja[r], r0, fma(jb[r], r1, acc[21 + r]));
+            acc[27] = fma(r0, r0, fma(r1, r1, acc[27]));
+            acc[28] += 1.0;
+        }
+        block_sum_lds<kPoseK>(acc, s_part, s_tot);
+        // from here on every lane holds the same numbers
+        const double* so = s_st[par];
+        const double Fn = 0.5 * s_tot[27], nvn = s_tot[28];
+        const bool trial = !first;
+        bool accept = false;
+        double mu, nu, dmax, h[6];
+        if (first) {
+            first = false;
+            if (nvn < 3.0) {
+                if (threadIdx.x == 0) {
+                    a.status[view] = ACM_POSE_TOO_FEW_OBSERVATIONS;
+                    if (a.cost) a.cost[view] = qnan;
+                    if (a.n_valid) a.n_valid[view] = (uint32_t)nvn;
+                    if (a.iters) a.iters[view] = 0;
+                    if (a.info) {
+#pragma unroll
+                        for (int k = 0; k < 21; ++k) a.info[21 * view + k] = 0.0;
+                    }
+                }
+                return;
+            }
+            accept = true;
+            mu = a.mu0;
+            nu = 2.0;
+            dmax = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                dmax = fmax(dmax, s_tot[pose_ut(k, k)]);
+                h[k] = 0.0;
+            }
+            if (a.max_it == 0) term = 1;
+            else if (!__builtin_isfinite(Fn)) term = 2;
+        } else {
+            mu = so[kStMu];
+            nu = so[kStNu];
+            dmax = so[kStDmax];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) h[k] = so[kStH + k];
+            // predicted reduction L(0) - L(h) = -(g.h + 0.5 h.A.h)
+            double gh = 0.0, hAh = 0.0;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                gh += so[kStG + i] * h[i];
+                double t = 0.0;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) t += so[kStA + pose_ut(i, j)] * h[j];
+                hAh += h[i] * t;
+            }
+            const double pred = -(gh + 0.5 * hAh);
+            const double rho =
+                (__builtin_isfinite(Fn) && pred > 0.0) ? (so[kStF] - Fn) / pred : -1.0;
+            if (rho > 0.0) {
+                accept = true;
+                const double t = 2.0 * rho - 1.0;
+                mu *= fmax(1.0 / 3.0, 1.0 - t * t * t);
+                nu = 2.0;
+            } else {
+                mu *= nu;
+                nu *= 2.0;
+                if (!__builtin_isfinite(mu) || mu > 1e32) term = 2;
+            }
+        }
+        // the accepted point after this evaluation: the totals and the pose
+        // just evaluated, or the state as it was
+        const double* Ap = accept ? static_cast<const double*>(s_tot) : so + kStA;
+        const double* gp = accept ? static_cast<const double*>(s_tot) + 21 : so + kStG;
+        const double F = accept ? Fn : so[kStF], nv = accept ? nvn : so[kStNv];
+        double cur[12], x[6];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) cur[k] = accept ? ev[k] : so[kStCur + k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) x[k] = !trial ? 0.0 : (accept ? so[kStXn + k] : so[kStX + k]);
+        if (accept && term == 0) {
+            double gi = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) gi = fmax(gi, fabs(gp[k]));
+            if (gi <= a.gtol) term = 1;
+            else if (trial && so[kStF] - Fn <= a.ctol * so[kStF]) term = 1;
+        }
+        // advance to the next pose to evaluate, or end
+        bool need = false;
+        double xn[6];
+        while (term == 0 && it < a.max_it) {
+            ++it;
+            double Ad[21], mg[6], hs[6];
+#pragma unroll
+            for (int k = 0; k < 21; ++k) Ad[k] = Ap[k];
+            const double floor_d = 1e-12 * fmax(dmax, 1.0);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                Ad[pose_ut(k, k)] += mu * fmax(Ad[pose_ut(k, k)], floor_d);
+                mg[k] = -gp[k];
+            }
+            if (!pose_chol6(Ad, mg, hs)) {
+                mu *= nu;
+                nu *= 2.0;
+                continue;
+            }
+            double hn = 0.0, xnorm = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                xn[k] = x[k] + hs[k];
+                h[k] = xn[k] - x[k];
+                hn += h[k] * h[k];
+                xnorm += x[k] * x[k];
+            }
+            hn = sqrt(hn);
+            xnorm = sqrt(xnorm);
+            if (hn <= a.ptol * (xnorm + a.ptol)) {
+                term = 1;
+                break;
+            }
+            need = true;
+            break;
+        }
+        if (!need) {
+            if (threadIdx.x == 0) {
+                double* dst = reinterpret_cast<double*>(a.poses + view);
+#pragma unroll
+                for (int k = 0; k < 12; ++k) dst[k] = cur[k];
+                a.status[view] = term == 1 ? ACM_POSE_OK : ACM_POSE_NOT_CONVERGED;
+                if (a.cost) a.cost[view] = F;
+                if (a.n_valid) a.n_valid[view] = (uint32_t)nv;
+                if (a.iters) a.iters[view] = it;
+                if (a.info) {
+#pragma unroll
+                    for (int k = 0; k < 21; ++k) a.info[21 * view + k] = Ap[k];
+                }
+            }
+            return;
+        }
+        if (threadIdx.x == 0) {
+            double* sn = s_st[par ^ 1];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) sn[kStCur + k] = cur[k];
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                sn[kStX + k] = x[k];
+                sn[kStXn + k] = xn[k];
+                sn[kStH + k] = h[k];
+                sn[kStG + k] = gp[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 21; ++k) sn[kStA + k] = Ap[k];
+            sn[kStF] = F;
+            sn[kStNv] = nv;
+            sn[kStMu] = mu;
+            sn[kStNu] = nu;
+            sn[kStDmax] = dmax;
+        }
+        par ^= 1;
+        pose_retract_dev(cur, h, ev);
+    }
+}
+
 // ----------------------------------------------------- reprojection stats
 // One streaming pass.  The variance is not a second pass over the errors
 // (error_metrics.rs:92 sums (e - mean)^2 after the mean): each lane keeps
@@ -5774,6 +6180,69 @@ ACM_API int acm_triangulate(const acm_camera* cam, size_t n_views, const acm_pos
         hipLaunchKernelGGL(k_triangulate<TagT>, dim3(nb), dim3(kBlock), 0, s,
                            prep(*cam, false, true), a);
         return check_launch("acm_triangulate");
+    });
+}
+
+ACM_API void acm_pose_optimize_batch_default_config(acm_pose_batch_config* cfg) {
+    if (!cfg) return;
+    cfg->max_iterations = 20;
+    cfg->flags = 0;
+    cfg->cost_tolerance = 1e-6;
+    cfg->parameter_tolerance = 1e-8;
+    cfg->gradient_tolerance = 1e-6;
+    cfg->initial_damping = 1e-4;
+}
+
+// The kernel keeps everything in registers and LDS: the workspace is a
+// reserved 64 bytes, whatever the shape.
+ACM_API size_t acm_pose_optimize_batch_workspace_size(size_t, size_t) { return 64; }
+
+ACM_API int acm_pose_optimize_batch(const acm_camera* cam, size_t n_views, acm_pose* poses,
+                                    size_t n_points, const double* points_world,
+                                    const int64_t* view_offsets, size_t n_observations,
+                                    const int32_t* obs_point, const double* obs_uv,
+                                    const acm_pose_batch_config* cfg, uint8_t* status,
+                                    double* cost, uint32_t* n_valid, int32_t* iterations,
+                                    double* information, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
+    if (cfg->max_iterations < 0 || cfg->flags != 0)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "negative max_iterations or nonzero flags");
+    if (n_views == 0) return ACM_SUCCESS;
+    if (!poses || !view_offsets || !status || (n_points && !points_world) ||
+        (n_observations && (!obs_point || !obs_uv)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace ||
+        workspace_bytes < acm_pose_optimize_batch_workspace_size(n_views, n_observations))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "batched pose workspace too small");
+    if (n_views > (size_t)0x7fffffff)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many views for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_model(cam->model, [&](auto tag) -> int {
+        using TagT = decltype(tag);
+        PoseBatchArgs a;
+        a.n_points = n_points;
+        a.n_obs = n_observations;
+        a.poses = poses;
+        a.X = points_world;
+        a.offs = view_offsets;
+        a.pt = obs_point;
+        a.uv = obs_uv;
+        a.status = status;
+        a.cost = cost;
+        a.n_valid = n_valid;
+        a.iters = iterations;
+        a.info = information;
+        a.max_it = cfg->max_iterations;
+        a.ctol = cfg->cost_tolerance;
+        a.ptol = cfg->parameter_tolerance;
+        a.gtol = cfg->gradient_tolerance;
+        a.mu0 = cfg->initial_damping;
+        hipLaunchKernelGGL(k_pose_batch<TagT>, dim3((unsigned)n_views), dim3(kBlock), 0, s,
+                           prep(*cam), a);
+        return check_launch("acm_pose_optimize_batch");
     });
 }
 

@@ -584,6 +584,98 @@ ACM_API int acm_triangulate(const acm_camera *cam, size_t n_views, const acm_pos
                             uint32_t *n_valid, double *information, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* Batched pose refinement: the dual of acm_triangulate -- the world points
+ * are known, the unknowns are the poses (world -> camera, p_cam = R X + t),
+ * one independent 6 x 6 problem per view, all views in one launch with the
+ * Levenberg-Marquardt loop on the device.  One camera (intrinsics) serves all
+ * views.  Together with acm_triangulate this is an alternating bundle
+ * adjustment with no host round trip.
+ *
+ * poses: n_views acm_pose, in/out.  points_world: 3 n_points f64, AoS, read
+ * only.  Observations are CSR by view: view k owns observations
+ * view_offsets[k] .. view_offsets[k + 1] - 1, in that order (view_offsets:
+ * n_views + 1 entries; entries outside [0, n_observations] are clamped as
+ * acm_triangulate clamps its offsets, so no offset can make the call read
+ * out of bounds).  Observation j is the pixel obs_uv[2 j], obs_uv[2 j + 1] of
+ * world point obs_point[j].
+ *
+ * An observation is valid iff its pixel is finite, obs_point[j] lies in
+ * [0, n_points), the world point is finite (acm_triangulate writes NaN for
+ * the points it could not solve; this call takes its output as it is) and
+ * the projection of R X + t (the fast projection of
+ * acm_pose_normal_equations) is Ok at the pose being evaluated; anything else
+ * is skipped -- an out-of-range index is never dereferenced and is no error
+ * of the call.  The count of valid observations is n_valid.
+ *
+ * Per view the problem is acm_pose_optimize's: r = project(p) - uv,
+ * J = Jp [I | -[p]x], left perturbation delta = (rho, phi), R <- Exp(phi) R,
+ * t <- Exp(phi) t + rho (acm_pose_retract's formulas, in double on the
+ * device), acm_lm_optimize's state machine with P = 6 and no bounds in local
+ * coordinates: the same damping, update, tolerances and constants.  A
+ * tolerance ends the loop: ACM_POSE_OK.  The iteration limit, a non-finite
+ * start cost or damping > 1e32: ACM_POSE_NOT_CONVERGED, with the best
+ * accepted pose written.  Fewer than 3 valid observations at the start pose:
+ * ACM_POSE_TOO_FEW_OBSERVATIONS, the pose left as given bit for bit, cost =
+ * NaN, information = 0, iterations = 0, n_valid = the count.  max_iterations
+ * = 0: the pose unchanged bit for bit, ACM_POSE_OK, cost / n_valid /
+ * information evaluated there.
+ *
+ * Outputs per view: poses, status (acm_pose_status, required), and when
+ * non-NULL cost (0.5 sum ||r||^2 at the returned pose), n_valid, iterations,
+ * information (the 21 upper-triangle entries of the undamped J^T J at the
+ * returned pose, row by row, parameters in the order rho, phi).
+ *
+ * A view's outputs depend only on its own observation list in order, the
+ * world points those observations name, its start pose, the camera and the
+ * config -- not on n_views, its index, the other views or the launch: the
+ * same view gives the same bits anywhere in any batch, and repeated calls
+ * return the same bits.  One 256-lane workgroup per view; a view with at
+ * most ACM_POSE_BATCH_STAGE_OBSERVATIONS observations stages them (pixel and
+ * gathered point, 40 B each) in LDS once, a longer one gathers from global
+ * memory at every evaluation (the same arithmetic in the same order).  Only
+ * n_views workgroups run; measured down to 8 views of 5000 observations the
+ * call is still 7x faster than one acm_pose_optimize per view, and a few
+ * views far longer than that (where acm_pose_optimize spreads one view over
+ * the whole device) were not measured.  The default
+ * of 20 iterations is acm_triangulate's, not acm_lm_default_config's 100.
+ *
+ * Errors: NULL cam / poses / view_offsets / cfg / status, NULL points_world
+ * with n_points > 0, NULL obs_point / obs_uv with n_observations > 0,
+ * negative max_iterations or nonzero flags: ACM_ERR_INVALID_ARGUMENT; a bad
+ * model: ACM_ERR_INVALID_MODEL; a NULL or short workspace (device,
+ * acm_pose_optimize_batch_workspace_size bytes): ACM_ERR_WORKSPACE_TOO_SMALL.
+ * n_views = 0 is valid and touches nothing.  Stream-ordered, no allocation,
+ * no host synchronisation, reentrant. */
+typedef enum acm_pose_status {
+    ACM_POSE_OK = 0,
+    ACM_POSE_TOO_FEW_OBSERVATIONS = 1, /* fewer than 3 valid observations at the start pose */
+    ACM_POSE_NOT_CONVERGED = 2         /* iteration limit or damping overflow; best accepted pose written */
+} acm_pose_status;
+
+/* observations of one view staged in LDS (40 B each); a longer view is read
+ * from global memory at every evaluation */
+#define ACM_POSE_BATCH_STAGE_OBSERVATIONS 1024
+
+typedef struct acm_pose_batch_config {
+    int32_t max_iterations;      /* per view; 0 = evaluate only.  default 20 */
+    int32_t flags;               /* must be 0 */
+    double cost_tolerance;       /* defaults of acm_lm_default_config: 1e-6 */
+    double parameter_tolerance;  /* 1e-8 */
+    double gradient_tolerance;   /* 1e-6 */
+    double initial_damping;      /* 1e-4 */
+} acm_pose_batch_config;
+
+ACM_API void acm_pose_optimize_batch_default_config(acm_pose_batch_config *cfg);
+ACM_API size_t acm_pose_optimize_batch_workspace_size(size_t n_views, size_t n_observations);
+ACM_API int acm_pose_optimize_batch(const acm_camera *cam, size_t n_views, acm_pose *poses,
+                                    size_t n_points, const double *points_world,
+                                    const int64_t *view_offsets, size_t n_observations,
+                                    const int32_t *obs_point, const double *obs_uv,
+                                    const acm_pose_batch_config *cfg, uint8_t *status,
+                                    double *cost, uint32_t *n_valid, int32_t *iterations,
+                                    double *information, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
 /* (r06) The sharded conversion's collectives.  One
  * process per GPU, each holding a shard of the correspondences; both
  * collectives are stream-ordered on device f64 buffers:
