@@ -15,7 +15,8 @@ from .camera import (CameraModel, CameraModelError, DoubleSphereModel, EucmModel
                      Resolution, UcmModel)
 from .util import (ImageQualityMetrics, calculate_psnr, calculate_ssim,  # noqa: E402
                    compute_image_quality_metrics)
-from .optimizer import (Pose, PoseBatchConfig, PoseBatchResult, TriangulationConfig,  # noqa: E402
+from .optimizer import (CalibrationConfig, CalibrationResult, Pose, PoseBatchConfig,  # noqa: E402
+                        PoseBatchResult, TriangulationConfig, calibrate,
                         TriangulationResult, alternate_bundle_adjustment, refine_pose,
                         refine_poses, tracks_by_view, tracks_from_dense, triangulate)
 
@@ -25,5 +26,6 @@ __all__ = [
     "Resolution", "UcmModel", "ImageQualityMetrics", "calculate_psnr", "calculate_ssim",
     "compute_image_quality_metrics", "Pose", "refine_pose", "triangulate", "tracks_from_dense",
     "TriangulationConfig", "TriangulationResult", "PoseBatchConfig", "PoseBatchResult",
+    "CalibrationConfig", "CalibrationResult", "calibrate",
     "refine_poses", "tracks_by_view", "alternate_bundle_adjustment",
 ]

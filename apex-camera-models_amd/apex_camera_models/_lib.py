@@ -131,6 +131,39 @@ POSE_OK, POSE_TOO_FEW_OBSERVATIONS, POSE_NOT_CONVERGED = 0, 1, 2
 POSE_BATCH_STAGE_OBSERVATIONS = 1024
 
 
+class CalibrateConfig(ctypes.Structure):
+    """acm_calibrate_config (include/acm.h)."""
+    _fields_ = [
+        ("max_iterations", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("cost_tolerance", ctypes.c_double),
+        ("parameter_tolerance", ctypes.c_double),
+        ("gradient_tolerance", ctypes.c_double),
+        ("initial_damping", ctypes.c_double),
+        ("fixed_mask", ctypes.c_uint32),
+        ("has_bounds", ctypes.c_uint32),
+        ("lower", ctypes.c_double * 9),
+        ("upper", ctypes.c_double * 9),
+    ]
+
+
+class CalibrateSummary(ctypes.Structure):
+    """acm_calibrate_summary (include/acm.h)."""
+    _fields_ = [
+        ("iterations", ctypes.c_int32),
+        ("termination", ctypes.c_int32),
+        ("evaluations", ctypes.c_int32),
+        ("n_views_used", ctypes.c_int32),
+        ("initial_cost", ctypes.c_double),
+        ("final_cost", ctypes.c_double),
+        ("n_valid", ctypes.c_double),
+        ("information", ctypes.c_double * 81),
+    ]
+
+
+CALIBRATE_SYSTEM_SIDE = 16  # view_system: 16 x 16 doubles per view
+
+
 class CellGrid(ctypes.Structure):
     """acm_cell_grid (include/acm.h, r06): the grid of a cell-form sample."""
     _fields_ = [
@@ -216,6 +249,9 @@ EXPORTED_SYMBOLS = (
     "acm_pose_optimize_batch_default_config",
     "acm_pose_optimize_batch_workspace_size",
     "acm_pose_optimize_batch",
+    "acm_calibrate_default_config",
+    "acm_calibrate_workspace_size",
+    "acm_calibrate",
     "acm_sample_points_cells",
     "acm_rccl_available",
     "acm_rccl_unique_id",
@@ -409,6 +445,14 @@ def load():
     L.acm_pose_optimize_batch.argtypes = [cam_p, sz, vp, sz, vp, vp, sz, vp, vp, pb_p, vp, vp, vp,
                                           vp, vp, vp, sz, vp]
     L.acm_pose_optimize_batch.restype = i
+    cal_p = ctypes.POINTER(CalibrateConfig)
+    L.acm_calibrate_default_config.argtypes = [cal_p]
+    L.acm_calibrate_default_config.restype = None
+    L.acm_calibrate_workspace_size.argtypes = [i, sz, sz]
+    L.acm_calibrate_workspace_size.restype = sz
+    L.acm_calibrate.argtypes = [cam_p, sz, vp, sz, vp, vp, sz, vp, vp, cal_p,
+                                ctypes.POINTER(CalibrateSummary), vp, vp, vp, vp, vp, sz, vp]
+    L.acm_calibrate.restype = i
     L.acm_sample_points_cells.argtypes = [cam_p, sz, sz, sz, i, vp, vp, vp, vp, vp, sz, vp]
     L.acm_sample_points_cells.restype = i
     L.acm_reprojection_error_cells.argtypes = [cam_p, sz, vp, i, vp, grid_p, vp, vp, vp, sz, vp]

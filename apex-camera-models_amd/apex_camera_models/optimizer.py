@@ -471,3 +471,99 @@ def alternate_bundle_adjustment(model: CameraModel, poses, track_offsets, obs_vi
         tri = triangulate(model, pt, offs, view, uv, initial=tri.points)
         costs.append(torch.nansum(tri.cost))
     return pt, tri, costs
+
+
+# ------------------------------------------------------ multi-view calibration
+@dataclass
+class CalibrationConfig:
+    """acm_calibrate_config; the defaults are acm_calibrate_default_config's.
+    bounds: parameter index -> (lower, upper), on the intrinsics only."""
+    max_iterations: int = 50
+    cost_tolerance: float = 1e-6
+    parameter_tolerance: float = 1e-8
+    gradient_tolerance: float = 1e-6
+    initial_damping: float = 1e-4
+    bounds: Optional[Dict[int, Tuple[float, float]]] = None
+
+
+@dataclass
+class CalibrationResult:
+    """model: a new camera model with the calibrated intrinsics; poses (K, 12)
+    f64, status (K,) u8 (_lib.POSE_*), cost (K,) f64 (NaN for a view that did
+    not take part), n_valid (K,) i32: device tensors, one row per view;
+    summary: an LmResult over the whole problem (its parameters the
+    intrinsics) with n_views_used added; information (P, P) f64 host tensor,
+    the reduced (Schur) normal matrix of the intrinsics; view_system (K, 16,
+    16) device f64 or None."""
+    model: CameraModel
+    poses: torch.Tensor
+    status: torch.Tensor
+    cost: torch.Tensor
+    n_valid: torch.Tensor
+    summary: LmResult
+    information: torch.Tensor
+    view_system: Optional[torch.Tensor] = None
+    n_views_used: int = 0
+
+
+def calibrate(model: CameraModel, poses, points_world, view_offsets, obs_point, obs_uv,
+              config: Optional[CalibrationConfig] = None, fixed: Optional[Sequence[int]] = None,
+              want_view_system: bool = False) -> CalibrationResult:
+    """Multi-view calibration (acm_calibrate): the model's intrinsics and
+    every view's pose from known world points, one Levenberg-Marquardt on the
+    joint problem through the Schur complement.  Inputs as refine_poses
+    (tracks_by_view's output feeds the call unchanged); neither `model` nor
+    the caller's pose tensor is modified.  fixed: indices of intrinsics held
+    at their start value."""
+    L = _lib.load()
+    pt = _poses_tensor(poses).clone()
+    pw = _as_device_f64(points_world, 3)
+    offs = torch.as_tensor(view_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    idx = torch.as_tensor(obs_point).to(device="cuda", dtype=torch.int32).contiguous()
+    uv = _as_device_f64(obs_uv, 2)
+    k, n, m = pt.shape[0], pw.shape[0], idx.shape[0]
+    if offs.shape[0] != k + 1 or uv.shape[0] != m:
+        raise ValueError("view_offsets needs K + 1 entries; obs_point and obs_uv one row per observation")
+    c = config or CalibrationConfig()
+    cfg = _lib.CalibrateConfig()
+    L.acm_calibrate_default_config(ctypes.byref(cfg))
+    cfg.max_iterations = c.max_iterations
+    cfg.cost_tolerance = c.cost_tolerance
+    cfg.parameter_tolerance = c.parameter_tolerance
+    cfg.gradient_tolerance = c.gradient_tolerance
+    cfg.initial_damping = c.initial_damping
+    if c.bounds:
+        cfg.has_bounds = 1
+        for j, (lo, hi) in c.bounds.items():
+            cfg.lower[j] = lo
+            cfg.upper[j] = hi
+    for j in fixed or ():
+        if not 0 <= int(j) < 32:
+            raise ValueError("fixed takes parameter indices")
+        cfg.fixed_mask |= 1 << int(j)
+    p = model.NUM_PARAMS
+    status = torch.empty((k,), dtype=torch.uint8, device="cuda")
+    cost = torch.empty((k,), dtype=torch.float64, device="cuda")
+    n_valid = torch.empty((k,), dtype=torch.int32, device="cuda")
+    vsys = torch.empty((k, 16, 16), dtype=torch.float64, device="cuda") if want_view_system else None
+    ws_bytes = L.acm_calibrate_workspace_size(model.MODEL_ID, k, m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device="cuda")
+    cam = model.acm_camera()
+    summ = _lib.CalibrateSummary()
+    _lib.check(L.acm_calibrate(
+        ctypes.byref(cam), k, pt.data_ptr() if k else None, n, pw.data_ptr() if n else None,
+        offs.data_ptr(), m, idx.data_ptr() if m else None, uv.data_ptr() if m else None,
+        ctypes.byref(cfg), ctypes.byref(summ), status.data_ptr() if k else None,
+        cost.data_ptr() if k else None, n_valid.data_ptr() if k else None,
+        vsys.data_ptr() if vsys is not None and k else None, ws.data_ptr(), ws_bytes,
+        _stream_handle()))
+    params = list(cam.params)[:p]
+    res = type(model.resolution)(model.resolution.width, model.resolution.height)
+    out = type(model)._from_params(params, res)
+    info = torch.tensor(list(summ.information)[: p * p], dtype=torch.float64).reshape(p, p)
+    summary = LmResult(parameters=params, iterations=summ.iterations,
+                       termination=_lib.LM_TERMINATION.get(summ.termination, "?"),
+                       evaluations=summ.evaluations, initial_cost=summ.initial_cost,
+                       final_cost=summ.final_cost, n_valid=int(summ.n_valid))
+    return CalibrationResult(out, pt, status, cost, n_valid, summary, info, vsys,
+                             summ.n_views_used)

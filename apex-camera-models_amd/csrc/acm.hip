@@ -31,6 +31,7 @@
 
 #include "acm.h"
 #include "camera_models.hpp"
+#include "lm_core.hpp"
 #include "lm_doorbell.hpp"
 
 namespace acm {
@@ -2269,6 +2270,421 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
         par ^= 1;
         pose_retract_dev(cur, h, ev);
     }
+}
+
+// ------------------------------------------------------------ calibration
+// acm_calibrate: the intrinsics (shared) and every view's pose in one LM.  The
+// Hessian is an arrow, so a state is evaluated per view (k_calib_eval: the
+// view's 16 x 16 Gram matrix of [Jpose | Jtheta | 0 | r]) and a step is the
+// Schur complement onto the intrinsics (k_calib_schur, k_calib_reduce), the
+// P x P solve on the host, the poses' back-substitution and retraction
+// (k_calib_backsub).  k_calib_totals sums what the host's accept / reject
+// needs.  The state lives in two workspace slots (poses, systems, counts);
+// accepting a trial swaps them.  No kernel waits on another workgroup: every
+// cross-view sum is a later launch's ordered loop.
+constexpr int kCalN = 16;          // the system's side: 6 + P <= 15, then the residual
+constexpr int kCalSys = kCalN * kCalN;
+constexpr int kCalTileLd = 17;     // doubles per tile row: lanes' row writes spread over the banks
+typedef double calib_d4 __attribute__((ext_vector_type(4)));
+
+struct CalibEvalArgs {
+    size_t n_points, n_obs;
+    const double* poses;  // [K][12]: the poses under evaluation
+    const double* X;
+    const int64_t* offs;
+    const int32_t* pt;
+    const double* uv;
+    double* sys;          // [K][256]
+    uint32_t* nv;         // [K]
+};
+
+// One 64 x 16 slab of rows (one per lane, zero when the lane has none) into
+// the wave's Gram accumulator: the lane writes its row to the wave's LDS
+// tile; for rows 4 s .. 4 s + 3 both operands of v_mfma_f64_16x16x4_f64 are
+// tile[4 s + (lane >> 4)][lane & 15] (A[i][k] = M[k][i] sits in lane i + 16 k,
+// B[k][j] = M[k][j] in lane j + 16 k), so one LDS read and one MFMA add the
+// rank-4 update to all 256 sums.  Only the wave touches its tile.
+__device__ __forceinline__ void calib_gram_rows(double* tile, const double (&row)[kCalN],
+                                                calib_d4& acc) {
+    const int lane = threadIdx.x & 63;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int cidx = 0; cidx < kCalN; ++cidx) tile[lane * kCalTileLd + cidx] = row[cidx];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int sl = 0; sl < 16; ++sl) {
+        const double m = tile[(4 * sl + (lane >> 4)) * kCalTileLd + (lane & 15)];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(m, m, acc, 0, 0, 0);
+    }
+}
+
+template <class TagT>
+__global__ __launch_bounds__(kBlock) void k_calib_eval(CamArg cam, CalibEvalArgs a) {
+    using M = typename TagT::template type<double>;
+    constexpr int P = M::P;
+    static_assert(6 + P < kCalN, "the residual column is the last");
+    __shared__ double s_obs[5][kPoseStageObs];  // x, y, z, u, v of the staged observations
+    __shared__ double s_tile[kBlock / 64][64 * kCalTileLd];
+    __shared__ uint32_t s_nv[kBlock / 64];
+    const Cam<double> c = make_cam<double>(cam);
+    const size_t view = blockIdx.x;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    // the view's observations, clamped into [0, n_obs] (k_pose_batch)
+    const long long nobs = (long long)a.n_obs;
+    long long ob = a.offs[view], oe = a.offs[view + 1];
+    ob = ob < 0 ? 0 : (ob > nobs ? nobs : ob);
+    oe = oe < ob ? ob : (oe > nobs ? nobs : oe);
+    const long long cnt = oe - ob;
+    const bool staged = cnt <= (long long)kPoseStageObs;  // workgroup-uniform
+    const double qnan = __builtin_nan("");
+    auto gather = [&](long long j, double& X, double& Y, double& Z, double& u, double& v) {
+        const int32_t pi = a.pt[ob + j];
+        u = a.uv[2 * (ob + j)];
+        v = a.uv[2 * (ob + j) + 1];
+        X = Y = Z = qnan;
+        if (pi >= 0 && (size_t)pi < a.n_points) {
+            X = a.X[3 * (size_t)pi];
+            Y = a.X[3 * (size_t)pi + 1];
+            Z = a.X[3 * (size_t)pi + 2];
+        }
+        if (!(__builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z))) X = Y = Z = qnan;
+    };
+    if (staged) {
+        for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+            double X, Y, Z, u, v;
+            gather(j, X, Y, Z, u, v);
+            s_obs[0][j] = X;
+            s_obs[1][j] = Y;
+            s_obs[2][j] = Z;
+            s_obs[3][j] = u;
+            s_obs[4][j] = v;
+        }
+        __syncthreads();
+    }
+    double ev[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) ev[k] = a.poses[12 * view + k];
+
+    double* tile = s_tile[wid];
+    calib_d4 acc = {0.0, 0.0, 0.0, 0.0};
+    uint32_t nvw = 0;  // the wave's valid observations (wave-uniform)
+    // every wave walks the same number of rounds; a round in which the wave
+    // has no valid observation would add zeros and is skipped (wave-uniform)
+    for (long long base = (long long)wid * 64; base < cnt; base += kBlock) {
+        const long long j = base + lane;
+        double ru[kCalN], rv[kCalN];
+#pragma unroll
+        for (int k = 0; k < kCalN; ++k) ru[k] = rv[k] = 0.0;
+        bool ok = false;
+        if (j < cnt) {
+            double X, Y, Z, ou, ov;
+            if (staged) {
+                X = s_obs[0][j];
+                Y = s_obs[1][j];
+                Z = s_obs[2][j];
+                ou = s_obs[3][j];
+                ov = s_obs[4][j];
+            } else {
+                gather(j, X, Y, Z, ou, ov);
+            }
+            if (__builtin_isfinite(ou) && __builtin_isfinite(ov) && __builtin_isfinite(X)) {
+                const double px = ev[0] * X + ev[1] * Y + ev[2] * Z + ev[9];
+                const double py = ev[3] * X + ev[4] * Y + ev[5] * Z + ev[10];
+                const double pz = ev[6] * X + ev[7] * Y + ev[8] * Z + ev[11];
+                double u, v, ju[P + 3], jv[P + 3];
+                if (M::template project<true, true, false, true>(c, px, py, pz, u, v, ju, jv) ==
+                    ST_OK) {
+                    ok = true;
+                    const double* qu = ju + P;
+                    const double* qv = jv + P;
+                    ru[0] = qu[0]; ru[1] = qu[1]; ru[2] = qu[2];
+                    ru[3] = py * qu[2] - pz * qu[1];
+                    ru[4] = pz * qu[0] - px * qu[2];
+                    ru[5] = px * qu[1] - py * qu[0];
+                    rv[0] = qv[0]; rv[1] = qv[1]; rv[2] = qv[2];
+                    rv[3] = py * qv[2] - pz * qv[1];
+                    rv[4] = pz * qv[0] - px * qv[2];
+                    rv[5] = px * qv[1] - py * qv[0];
+#pragma unroll
+                    for (int k = 0; k < P; ++k) {
+                        ru[6 + k] = ju[k];
+                        rv[6 + k] = jv[k];
+                    }
+                    ru[kCalN - 1] = u - ou;
+                    rv[kCalN - 1] = v - ov;
+                }
+            }
+        }
+        const unsigned long long any = __ballot(ok);
+        if (any == 0) continue;
+        nvw += (uint32_t)__popcll(any);
+        calib_gram_rows(tile, ru, acc);
+        calib_gram_rows(tile, rv, acc);
+    }
+    // the four waves' sums, added in wave order: C/D of the f64 MFMA has
+    // col = lane & 15, row = (lane >> 4) + 4 reg
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tile[((lane >> 4) + 4 * r) * kCalN + (lane & 15)] = acc[r];
+    if (lane == 0) s_nv[wid] = nvw;
+    __syncthreads();
+    double s = 0.0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) s += s_tile[w][threadIdx.x];
+    a.sys[(size_t)kCalSys * view + threadIdx.x] = s;
+    if (threadIdx.x == 0) {
+        uint32_t n = 0;
+#pragma unroll
+        for (int w = 0; w < kBlock / 64; ++w) n += s_nv[w];
+        a.nv[view] = n;
+    }
+}
+
+struct CalibStepArgs {
+    size_t n_views;
+    int P;
+    const double* sys;      // [K][256] at the accepted state
+    const uint32_t* nv;     // [K] of the state just evaluated
+    uint8_t* status;        // [K]: TOO_FEW or not, fixed by the first totals
+    double* schur;          // [K][256]: rows 0-5 App^-1 [Apt | gp], rows 6.. Atp of that
+    uint32_t* bad;          // [K]: the view's damped pose block is not positive definite
+    double* part;           // [K][2]: predicted reduction and |delta_k|^2 of the trial step
+    double* red;            // k_calib_reduce's output (kCalRed doubles)
+    double* tot;            // k_calib_totals' output (kCalTot doubles)
+    const double* pose_cur; // [K][12]
+    double* pose_trial;     // [K][12]
+};
+constexpr int kCalRed = 2 * kCalSys + 2;  // sum of systems | sum of Schur blocks | any bad | pad
+// F, n_valid, predicted, |delta poses|^2, views used | diag(Att) 9 | max diag(App) |
+// max |gp| | g_theta 9
+constexpr int kCalTot = 25;
+constexpr int kCalBatch = 16;  // views whose loads an ordered sum issues together
+
+// After an evaluation (systems in a.sys, counts in a.nv): the sums over the
+// participating views, each by one thread in view order.  first: the start
+// state -- participation is decided here (3 valid observations) and written
+// to a.status for every later launch.
+__global__ __launch_bounds__(64) void k_calib_totals(CalibStepArgs a, const double* sys_eval,
+                                                     int first) {
+    const int t = threadIdx.x;
+    if (first)
+        for (size_t k = t; k < a.n_views; k += 64)
+            a.status[k] = a.nv[k] < 3 ? ACM_POSE_TOO_FEW_OBSERVATIONS : ACM_POSE_NOT_CONVERGED;
+    if (t >= kCalTot) return;
+    const bool is_max = t == 14 || t == 15;
+    // what thread t reads per view: base[stride k + off0 + r dstep], r < 6 (one
+    // entry six times when dstep == 0)
+    const double* base = sys_eval;
+    size_t stride = kCalSys;
+    int off0 = 0, dstep = 0;
+    double scale = 1.0;
+    bool absv = false, zero = false;
+    if (t == 0) {
+        off0 = kCalSys - 1;
+        scale = 0.5;
+    } else if (t == 2 || t == 3) {
+        base = a.part;
+        stride = 2;
+        off0 = t - 2;
+        zero = first != 0;
+    } else if (t >= 5 && t < 14) {
+        off0 = (6 + t - 5) * (kCalN + 1);
+    } else if (t == 14) {
+        dstep = kCalN + 1;
+    } else if (t == 15) {
+        off0 = kCalN - 1;
+        dstep = kCalN;
+        absv = true;
+    } else if (t >= 16) {
+        off0 = (6 + t - 16) * kCalN + kCalN - 1;
+    }
+    // kCalBatch views at a time: first every count and status, then every
+    // value, then the adds in view order -- no load waits on another, and a
+    // view past the end reads the last one's and is not added
+    const size_t last = a.n_views - 1;
+    double s = 0.0;
+    for (size_t k0 = 0; k0 < a.n_views; k0 += kCalBatch) {
+        uint32_t nvk[kCalBatch];
+        uint8_t stk[kCalBatch];
+        double v[kCalBatch];
+#pragma unroll
+        for (int i = 0; i < kCalBatch; ++i) {
+            const size_t k = k0 + i < last ? k0 + i : last;
+            nvk[i] = a.nv[k];
+            stk[i] = a.status[k];
+        }
+#pragma unroll
+        for (int i = 0; i < kCalBatch; ++i) {
+            const size_t k = k0 + i < last ? k0 + i : last;
+            double m = 0.0;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                double x = base[stride * k + off0 + r * dstep];
+                x = absv ? fabs(x) : x;
+                m = r == 0 ? x : fmax(m, x);
+            }
+            v[i] = t == 1 ? (double)nvk[i] : (t == 4 ? 1.0 : (zero ? 0.0 : scale * m));
+        }
+#pragma unroll
+        for (int i = 0; i < kCalBatch; ++i) {
+            const bool used = k0 + i <= last &&
+                              (first ? nvk[i] >= 3 : stk[i] != ACM_POSE_TOO_FEW_OBSERVATIONS);
+            const double sn = is_max ? fmax(s, v[i]) : s + v[i];
+            s = used ? sn : s;
+        }
+    }
+    a.tot[t] = s;
+}
+
+// Per participating view, 16 lanes: lane q solves (App + damping) y = column q
+// of the view's system for the intrinsics' columns and the residual's
+// (pose_chol6; every lane factors the same 6 x 6), then multiplies by Atp.
+__global__ __launch_bounds__(64) void k_calib_schur(CalibStepArgs a, double mu, double floor_d) {
+    const size_t view = (size_t)blockIdx.x * 4 + (threadIdx.x >> 4);
+    const int q = threadIdx.x & 15;
+    if (view >= a.n_views || a.status[view] == ACM_POSE_TOO_FEW_OBSERVATIONS) return;
+    const double* S = a.sys + (size_t)kCalSys * view;
+    double* O = a.schur + (size_t)kCalSys * view;
+    const bool active = (q >= 6 && q < 6 + a.P) || q == kCalN - 1;
+    if (!active) {
+#pragma unroll
+        for (int i = 0; i < kCalN; ++i) O[i * kCalN + q] = 0.0;
+        return;
+    }
+    double A[21], b[6], x[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+#pragma unroll
+        for (int cidx = r; cidx < 6; ++cidx) A[pose_ut(r, cidx)] = S[r * kCalN + cidx];
+        A[pose_ut(r, r)] += mu * fmax(A[pose_ut(r, r)], floor_d);
+        b[r] = S[r * kCalN + q];
+    }
+    const bool ok = pose_chol6(A, b, x);
+    if (q == kCalN - 1) a.bad[view] = ok ? 0u : 1u;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        if (!ok) x[r] = 0.0;
+        O[r * kCalN + q] = x[r];
+    }
+#pragma unroll
+    for (int i = 0; i < kCalN - 6; ++i) {
+        double tsum = 0.0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r) tsum += S[(6 + i) * kCalN + r] * x[r];
+        O[(6 + i) * kCalN + q] = i < a.P ? tsum : 0.0;
+    }
+}
+
+// The sums over the participating views, in view order, of the systems and
+// of the Schur blocks, entry by entry; and whether any view's block failed.
+__global__ __launch_bounds__(kCalSys) void k_calib_reduce(CalibStepArgs a) {
+    const int t = threadIdx.x;
+    double s0 = 0.0, s1 = 0.0;
+    int any = 0;
+    // kCalBatch views at a time: the statuses, then the entries, then the adds
+    // in view order -- no load waits on another.  A view past the end reads the
+    // last one's and is not added; a view that takes no part has no Schur
+    // block, and what is read there is not used.
+    const size_t last = a.n_views - 1;
+    for (size_t k0 = 0; k0 < a.n_views; k0 += kCalBatch) {
+        uint8_t stk[kCalBatch];
+        double v0[kCalBatch], v1[kCalBatch];
+#pragma unroll
+        for (int i = 0; i < kCalBatch; ++i) stk[i] = a.status[k0 + i < last ? k0 + i : last];
+#pragma unroll
+        for (int i = 0; i < kCalBatch; ++i) {
+            const size_t k = k0 + i < last ? k0 + i : last;
+            v0[i] = a.sys[(size_t)kCalSys * k + t];
+            v1[i] = a.schur[(size_t)kCalSys * k + t];
+        }
+#pragma unroll
+        for (int i = 0; i < kCalBatch; ++i) {
+            const bool used = k0 + i <= last && stk[i] != ACM_POSE_TOO_FEW_OBSERVATIONS;
+            const double n0 = s0 + v0[i], n1 = s1 + v1[i];
+            s0 = used ? n0 : s0;
+            s1 = used ? n1 : s1;
+        }
+    }
+    for (size_t k = t; k < a.n_views; k += kCalSys)
+        if (a.status[k] != ACM_POSE_TOO_FEW_OBSERVATIONS && a.bad[k]) any = 1;
+    any = __syncthreads_or(any);
+    a.red[t] = s0;
+    a.red[kCalSys + t] = s1;
+    if (t == 0) {
+        a.red[2 * kCalSys] = any ? 1.0 : 0.0;
+        a.red[2 * kCalSys + 1] = 0.0;
+    }
+}
+
+struct CalibH {
+    double v[ACM_MAX_PARAMS];  // the intrinsics' step, 0 for fixed and absent parameters
+};
+
+// One lane per view: delta_k = -(y_g + Y h), the view's share of the
+// predicted reduction over the full step (undamped system), and the trial
+// pose.  A view that does not participate keeps its pose.
+__global__ __launch_bounds__(64) void k_calib_backsub(CalibStepArgs a, CalibH h) {
+    const size_t view = (size_t)blockIdx.x * 64 + threadIdx.x;
+    if (view >= a.n_views) return;
+    double cur[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) cur[k] = a.pose_cur[12 * view + k];
+    if (a.status[view] == ACM_POSE_TOO_FEW_OBSERVATIONS) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) a.pose_trial[12 * view + k] = cur[k];
+        a.part[2 * view] = 0.0;
+        a.part[2 * view + 1] = 0.0;
+        return;
+    }
+    const double* S = a.sys + (size_t)kCalSys * view;
+    const double* Y = a.schur + (size_t)kCalSys * view;
+    double d[kCalN - 1], dp[6];
+#pragma unroll
+    for (int j = 0; j < ACM_MAX_PARAMS; ++j) d[6 + j] = h.v[j];
+    double hn2 = 0.0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        double sacc = Y[r * kCalN + kCalN - 1];
+#pragma unroll
+        for (int j = 0; j < ACM_MAX_PARAMS; ++j) sacc += Y[r * kCalN + 6 + j] * h.v[j];
+        d[r] = dp[r] = -sacc;
+        hn2 += dp[r] * dp[r];
+    }
+    double gh = 0.0, hAh = 0.0;
+#pragma unroll
+    for (int i = 0; i < kCalN - 1; ++i) {
+        gh += S[i * kCalN + kCalN - 1] * d[i];
+        double tsum = 0.0;
+#pragma unroll
+        for (int j = 0; j < kCalN - 1; ++j) tsum += S[i * kCalN + j] * d[j];
+        hAh += d[i] * tsum;
+    }
+    a.part[2 * view] = -(gh + 0.5 * hAh);
+    a.part[2 * view + 1] = hn2;
+    double out[12];
+    pose_retract_dev(cur, dp, out);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) a.pose_trial[12 * view + k] = out[k];
+}
+
+// The per-view outputs from the accepted slot.
+__global__ __launch_bounds__(kCalSys) void k_calib_finish(CalibStepArgs a, int converged,
+                                                          acm_pose* poses, double* view_cost,
+                                                          uint32_t* view_n_valid,
+                                                          double* view_system) {
+    const size_t view = blockIdx.x;
+    const int t = threadIdx.x;
+    const bool used = a.status[view] != ACM_POSE_TOO_FEW_OBSERVATIONS;
+    const double s = a.sys[(size_t)kCalSys * view + t];
+    if (view_system) view_system[(size_t)kCalSys * view + t] = s;
+    if (used && t < 12) reinterpret_cast<double*>(poses + view)[t] = a.pose_cur[12 * view + t];
+    if (t == kCalSys - 1 && view_cost) view_cost[view] = used ? 0.5 * s : __builtin_nan("");
+    if (t == 0 && view_n_valid) view_n_valid[view] = a.nv[view];
+    __syncthreads();
+    if (t == 0 && used && converged) a.status[view] = ACM_POSE_OK;
 }
 
 // ----------------------------------------------------- reprojection stats
@@ -6244,6 +6660,317 @@ ACM_API int acm_pose_optimize_batch(const acm_camera* cam, size_t n_views, acm_p
                            prep(*cam), a);
         return check_launch("acm_pose_optimize_batch");
     });
+}
+
+ACM_API void acm_calibrate_default_config(acm_calibrate_config* cfg) {
+    if (!cfg) return;
+    cfg->max_iterations = 50;
+    cfg->flags = 0;
+    cfg->cost_tolerance = 1e-6;
+    cfg->parameter_tolerance = 1e-8;
+    cfg->gradient_tolerance = 1e-6;
+    cfg->initial_damping = 1e-4;
+    cfg->fixed_mask = 0;
+    cfg->has_bounds = 0;
+    for (int i = 0; i < ACM_MAX_PARAMS; ++i) {
+        cfg->lower[i] = -INFINITY;
+        cfg->upper[i] = INFINITY;
+    }
+}
+
+// doubles: two pose slots, two system slots, the Schur blocks, the step
+// partials, k_calib_reduce's and k_calib_totals' outputs; then the uint32
+// counts (two slots) and the failure flags
+static size_t calib_ws_doubles(size_t k) {
+    return 2 * 12 * k + 2 * (size_t)kCalSys * k + (size_t)kCalSys * k + 2 * k + kCalRed + kCalTot + 1;
+}
+
+ACM_API size_t acm_calibrate_workspace_size(int model, size_t n_views, size_t) {
+    if (acm_num_params(model) < 0) return 0;
+    return calib_ws_doubles(n_views) * sizeof(double) + 3 * n_views * sizeof(uint32_t) + 64;
+}
+
+static int hip_rc(hipError_t e, const char* what);
+
+ACM_API int acm_calibrate(acm_camera* cam, size_t n_views, acm_pose* poses, size_t n_points,
+                          const double* points_world, const int64_t* view_offsets,
+                          size_t n_observations, const int32_t* obs_point, const double* obs_uv,
+                          const acm_calibrate_config* cfg, acm_calibrate_summary* summary,
+                          uint8_t* view_status, double* view_cost, uint32_t* view_n_valid,
+                          double* view_system, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
+    if (cfg->max_iterations < 0 || cfg->flags != 0)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "negative max_iterations or nonzero flags");
+    const int P = (int)cam->num_params;
+    if (cfg->fixed_mask >> P) return fail(ACM_ERR_INVALID_ARGUMENT, "fixed_mask names no parameter");
+    if (cfg->has_bounds)
+        for (int i = 0; i < P; ++i)
+            if (!(cfg->lower[i] <= cfg->upper[i]))
+                return fail(ACM_ERR_INVALID_ARGUMENT, "lower bound above upper bound");
+    if (n_views == 0) return ACM_SUCCESS;
+    if (!poses || !view_offsets || !view_status || (n_points && !points_world) ||
+        (n_observations && (!obs_point || !obs_uv)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace ||
+        workspace_bytes < acm_calibrate_workspace_size(cam->model, n_views, n_observations))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "calibration workspace too small");
+    if (n_views > (size_t)0x7fffffff)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many views for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t K = n_views;
+
+    // workspace
+    double* wd = reinterpret_cast<double*>(((uintptr_t)workspace + 7) & ~(uintptr_t)7);
+    double* pose_slot[2] = {wd, wd + 12 * K};
+    wd += 24 * K;
+    double* sys_slot[2] = {wd, wd + (size_t)kCalSys * K};
+    wd += 2 * (size_t)kCalSys * K;
+    double* schur = wd;
+    wd += (size_t)kCalSys * K;
+    double* part = wd;
+    wd += 2 * K;
+    double* red = wd;
+    wd += kCalRed;
+    double* tot = wd;
+    wd += kCalTot + 1;
+    uint32_t* wu = reinterpret_cast<uint32_t*>(wd);
+    uint32_t* nv_slot[2] = {wu, wu + K};
+    uint32_t* bad = wu + 2 * K;
+
+    const int free_n = P - __builtin_popcount(cfg->fixed_mask);
+    int fidx[ACM_MAX_PARAMS];
+    for (int i = 0, f = 0; i < P; ++i)
+        if (!((cfg->fixed_mask >> i) & 1u)) fidx[f++] = i;
+    auto clampf = [&](double* x) {
+        if (!cfg->has_bounds) return;
+        for (int f = 0; f < free_n; ++f) {
+            const int i = fidx[f];
+            x[i] = fmin(fmax(x[i], cfg->lower[i]), cfg->upper[i]);
+        }
+    };
+
+    int cur = 0;  // the accepted slot
+    auto step_args = [&](int sys_of, int nv_of) {
+        CalibStepArgs a;
+        a.n_views = K;
+        a.P = P;
+        a.sys = sys_slot[sys_of];
+        a.nv = nv_slot[nv_of];
+        a.status = view_status;
+        a.schur = schur;
+        a.bad = bad;
+        a.part = part;
+        a.red = red;
+        a.tot = tot;
+        a.pose_cur = pose_slot[cur];
+        a.pose_trial = pose_slot[cur ^ 1];
+        return a;
+    };
+    // evaluate the intrinsics x with the poses of a slot, sum, and fetch the totals
+    double ht[kCalTot];
+    auto evaluate = [&](const double* x, int slot, int first) -> int {
+        acm_camera c = *cam;
+        for (int i = 0; i < P; ++i) c.params[i] = x[i];
+        int r = dispatch_model(cam->model, [&](auto tag) -> int {
+            using TagT = decltype(tag);
+            CalibEvalArgs a;
+            a.n_points = n_points;
+            a.n_obs = n_observations;
+            a.poses = pose_slot[slot];
+            a.X = points_world;
+            a.offs = view_offsets;
+            a.pt = obs_point;
+            a.uv = obs_uv;
+            a.sys = sys_slot[slot];
+            a.nv = nv_slot[slot];
+            hipLaunchKernelGGL(k_calib_eval<TagT>, dim3((unsigned)K), dim3(kBlock), 0, s, prep(c),
+                               a);
+            return check_launch("acm_calibrate (evaluation)");
+        });
+        if (r) return r;
+        hipLaunchKernelGGL(k_calib_totals, dim3(1), dim3(64), 0, s, step_args(slot, slot),
+                           (const double*)sys_slot[slot], first);
+        if ((r = check_launch("acm_calibrate (totals)"))) return r;
+        if ((r = hip_rc(hipMemcpyAsync(ht, tot, sizeof(ht), hipMemcpyDeviceToHost, s),
+                        "hipMemcpyAsync(D2H)")))
+            return r;
+        return hip_rc(hipStreamSynchronize(s), "hipStreamSynchronize");
+    };
+    // the Schur blocks of the accepted state under damping mu, summed; hr <- red
+    double hr[kCalRed];
+    auto reduce = [&](double mu, double floor_d) -> int {
+        const CalibStepArgs a = step_args(cur, cur);
+        hipLaunchKernelGGL(k_calib_schur, dim3((unsigned)((K + 3) / 4)), dim3(64), 0, s, a, mu,
+                           floor_d);
+        int r = check_launch("acm_calibrate (Schur)");
+        if (r) return r;
+        hipLaunchKernelGGL(k_calib_reduce, dim3(1), dim3(kCalSys), 0, s, a);
+        if ((r = check_launch("acm_calibrate (reduce)"))) return r;
+        if ((r = hip_rc(hipMemcpyAsync(hr, red, sizeof(hr), hipMemcpyDeviceToHost, s),
+                        "hipMemcpyAsync(D2H)")))
+            return r;
+        return hip_rc(hipStreamSynchronize(s), "hipStreamSynchronize");
+    };
+    auto ginf = [&]() {  // of the totals in ht: the poses' and the free intrinsics' gradient
+        double m = ht[15];
+        for (int f = 0; f < free_n; ++f) m = fmax(m, fabs(ht[16 + fidx[f]]));
+        return m;
+    };
+
+    if ((rc = hip_rc(hipMemcpyAsync(pose_slot[0], poses, 12 * K * sizeof(double),
+                                    hipMemcpyDeviceToDevice, s),
+                     "hipMemcpyAsync(D2D)")))
+        return rc;
+    double x[ACM_MAX_PARAMS] = {0}, xn[ACM_MAX_PARAMS] = {0};
+    for (int i = 0; i < P; ++i) x[i] = cam->params[i];
+    if (cfg->max_iterations > 0) clampf(x);
+    if ((rc = evaluate(x, 0, 1))) return rc;
+    int it = 0, evals = 1, term = ACM_LM_MAX_ITERATIONS;
+    const int used = (int)ht[4];
+    double F = ht[0], nv = ht[1];
+    const double initial_cost = F;
+    double dmax = ht[14];
+    for (int i = 0; i < P; ++i) dmax = fmax(dmax, ht[5 + i]);
+    const double floor_d = 1e-12 * fmax(dmax, 1.0);
+    double mu = cfg->initial_damping, nu = 2.0;
+    if (used == 0 || !std::isfinite(F)) term = ACM_LM_FAILED;
+    else if (cfg->max_iterations > 0 && ginf() <= cfg->gradient_tolerance) term = ACM_LM_GRADIENT;
+
+    while (term == ACM_LM_MAX_ITERATIONS && it < cfg->max_iterations) {
+        ++it;
+        if ((rc = reduce(mu, floor_d))) return rc;
+        bool solved = hr[2 * kCalSys] == 0.0;
+        CalibH h;
+        for (int i = 0; i < ACM_MAX_PARAMS; ++i) h.v[i] = 0.0;
+        if (solved && free_n > 0) {
+            double Sd[81], mg[9], hs[9];
+            for (int fa = 0; fa < free_n; ++fa) {
+                const int ia = 6 + fidx[fa];
+                for (int fb = 0; fb < free_n; ++fb) {
+                    const int ib = 6 + fidx[fb];
+                    Sd[fa * free_n + fb] = hr[ia * kCalN + ib] - hr[kCalSys + ia * kCalN + ib];
+                }
+                const double ajj = hr[ia * kCalN + ia];
+                Sd[fa * free_n + fa] =
+                    (ajj + mu * fmax(ajj, floor_d)) - hr[kCalSys + ia * kCalN + ia];
+                mg[fa] = -(hr[ia * kCalN + kCalN - 1] - hr[kCalSys + ia * kCalN + kCalN - 1]);
+            }
+            solved = lm::cholesky_solve(free_n, Sd, mg, hs);
+            if (solved) {
+                for (int i = 0; i < P; ++i) xn[i] = x[i];
+                for (int f = 0; f < free_n; ++f) xn[fidx[f]] = x[fidx[f]] + hs[f];
+                clampf(xn);
+                for (int i = 0; i < P; ++i) h.v[i] = xn[i] - x[i];
+            }
+            // A parameter the clamp stopped is held at its clamped step and the
+            // others are solved again for it (at most free_n times): the plain
+            // projection of a coupled step (DS alpha against xi and fx) is no
+            // descent direction for the rest and the loop stalls.
+            bool held[ACM_MAX_PARAMS] = {false};
+            while (solved && cfg->has_bounds) {
+                bool more = false;
+                for (int f = 0; f < free_n; ++f)
+                    if (!held[f] && xn[fidx[f]] != x[fidx[f]] + hs[f]) held[f] = more = true;
+                if (!more) break;
+                int sub[ACM_MAX_PARAMS], ns = 0;
+                for (int f = 0; f < free_n; ++f)
+                    if (!held[f]) sub[ns++] = f;
+                if (ns == 0) break;
+                double Ss[81], ms[9], hsub[9];
+                for (int a = 0; a < ns; ++a) {
+                    ms[a] = mg[sub[a]];
+                    for (int f = 0; f < free_n; ++f)
+                        if (held[f]) ms[a] -= Sd[sub[a] * free_n + f] * h.v[fidx[f]];
+                    for (int b = 0; b < ns; ++b) Ss[a * ns + b] = Sd[sub[a] * free_n + sub[b]];
+                }
+                solved = lm::cholesky_solve(ns, Ss, ms, hsub);
+                if (!solved) break;
+                for (int a = 0; a < ns; ++a) {
+                    hs[sub[a]] = hsub[a];
+                    xn[fidx[sub[a]]] = x[fidx[sub[a]]] + hsub[a];
+                }
+                clampf(xn);
+                for (int i = 0; i < P; ++i) h.v[i] = xn[i] - x[i];
+            }
+        } else if (solved) {
+            for (int i = 0; i < P; ++i) xn[i] = x[i];
+        }
+        if (!solved) {
+            mu *= nu;
+            nu *= 2.0;
+            continue;
+        }
+        hipLaunchKernelGGL(k_calib_backsub, dim3((unsigned)((K + 63) / 64)), dim3(64), 0, s,
+                           step_args(cur, cur), h);
+        if ((rc = check_launch("acm_calibrate (back-substitution)"))) return rc;
+        if ((rc = evaluate(xn, cur ^ 1, 0))) return rc;
+        double hn2 = ht[3], xn2 = 0.0;
+        for (int i = 0; i < P; ++i) {
+            hn2 += h.v[i] * h.v[i];
+            xn2 += x[i] * x[i];
+        }
+        if (sqrt(hn2) <= cfg->parameter_tolerance * (sqrt(xn2) + cfg->parameter_tolerance)) {
+            term = ACM_LM_PARAMETER;
+            break;
+        }
+        ++evals;
+        const double Fn = ht[0], nvn = ht[1], pred = ht[2];
+        const double rho =
+            (std::isfinite(Fn) && pred > 0.0 && nvn >= nv) ? (F - Fn) / pred : -1.0;
+        if (rho > 0.0) {
+            const double dF = F - Fn, Fold = F;
+            cur ^= 1;
+            for (int i = 0; i < P; ++i) x[i] = xn[i];
+            F = Fn;
+            nv = nvn;
+            const double t = 2.0 * rho - 1.0;
+            mu *= fmax(1.0 / 3.0, 1.0 - t * t * t);
+            nu = 2.0;
+            if (ginf() <= cfg->gradient_tolerance) term = ACM_LM_GRADIENT;
+            else if (dF <= cfg->cost_tolerance * Fold) term = ACM_LM_COST;
+        } else {
+            mu *= nu;
+            nu *= 2.0;
+            if (!std::isfinite(mu) || mu > 1e32) term = ACM_LM_FAILED;
+        }
+    }
+
+    // the undamped reduced system at the returned state
+    double info[ACM_MAX_PARAMS * ACM_MAX_PARAMS];
+    for (int i = 0; i < ACM_MAX_PARAMS * ACM_MAX_PARAMS; ++i) info[i] = 0.0;
+    if (used > 0) {
+        if ((rc = reduce(0.0, 0.0))) return rc;
+        if (hr[2 * kCalSys] == 0.0)
+            for (int fa = 0; fa < free_n; ++fa)
+                for (int fb = 0; fb < free_n; ++fb) {
+                    const int ia = 6 + fidx[fa], ib = 6 + fidx[fb];
+                    info[fidx[fa] * P + fidx[fb]] =
+                        hr[ia * kCalN + ib] - hr[kCalSys + ia * kCalN + ib];
+                }
+    }
+    const int converged = cfg->max_iterations == 0 || term == ACM_LM_COST ||
+                          term == ACM_LM_PARAMETER || term == ACM_LM_GRADIENT;
+    hipLaunchKernelGGL(k_calib_finish, dim3((unsigned)K), dim3(kCalSys), 0, s,
+                       step_args(cur, cur), converged && used > 0 ? 1 : 0, poses, view_cost,
+                       view_n_valid, view_system);
+    if ((rc = check_launch("acm_calibrate (outputs)"))) return rc;
+    if ((rc = hip_rc(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+    if (used > 0)
+        for (int i = 0; i < P; ++i) cam->params[i] = x[i];
+    if (summary) {
+        summary->iterations = it;
+        summary->termination = term;
+        summary->evaluations = evals;
+        summary->n_views_used = used;
+        summary->initial_cost = initial_cost;
+        summary->final_cost = F;
+        summary->n_valid = nv;
+        for (int i = 0; i < ACM_MAX_PARAMS * ACM_MAX_PARAMS; ++i) summary->information[i] = info[i];
+    }
+    return ACM_SUCCESS;
 }
 
 ACM_API size_t acm_reprojection_stats_workspace_size(size_t n) {

@@ -67,7 +67,10 @@
 // returns the finite limit of the off-axis block, FOV's small-r branch the
 // derivative of its constant rd); formulas in DESIGN.md 8.1.  The reference
 // has no counterpart; tests hold it to 1e-10 of the point's largest entry
-// against 50-digit derivatives (observed < 1e-15).
+// against 50-digit derivatives (observed < 1e-15).  WJ and PJ together (the
+// calibration kernel): one projection returns both, the parameter Jacobian in
+// ju / jv[0..P) as with WJ alone and the point Jacobian behind it, ju / jv
+// [P..P + 3) -- the same expressions as either alone.
 //
 // Reference citations: /root/reference/src/camera/<model>.rs:line.
 #pragma once
@@ -473,9 +476,11 @@ struct Pinhole {
             jv[0] = T(0); jv[1] = yz; jv[2] = T(0); jv[3] = T(1);
         }
         if (PJ) {  // u = fx x / z + cx
+            T* const pu = ju + (WJ ? P : 0);  // beside the parameter Jacobian when both
+            T* const pv = jv + (WJ ? P : 0);
             const T r = FAST ? iz : rz;
-            ju[0] = fx * r; ju[1] = T(0); ju[2] = -(fxx * r);
-            jv[0] = T(0); jv[1] = fy * r; jv[2] = -(fyy * r);
+            pu[0] = fx * r; pu[1] = T(0); pu[2] = -(fxx * r);
+            pv[0] = T(0); pv[1] = fy * r; pv[2] = -(fyy * r);
         }
         return st;
     }
@@ -541,6 +546,8 @@ struct RadTan {
             jv[8] = fy * yp * r6;
         }
         if (PJ) {
+            T* const pu = ju + (WJ ? P : 0);  // beside the parameter Jacobian when both
+            T* const pv = jv + (WJ ? P : 0);
             // d(xd, yd) / d(xp, yp) = [[a00, a01], [a01, a11]], then
             // d(xp) = (1/z, 0, -xp/z), d(yp) = (0, 1/z, -yp/z)
             const T r = FAST ? iz : rz;
@@ -549,8 +556,8 @@ struct RadTan {
             const T a01 = dr * xp * yp + T(2) * p1 * xp + T(2) * p2 * yp;
             const T a11 = radial + dr * yp * yp + T(6) * p1 * yp + T(2) * p2 * xp;
             const T fr = fx * r, gr = fy * r;
-            ju[0] = fr * a00; ju[1] = fr * a01; ju[2] = -(fr * (a00 * xp + a01 * yp));
-            jv[0] = gr * a01; jv[1] = gr * a11; jv[2] = -(gr * (a01 * xp + a11 * yp));
+            pu[0] = fr * a00; pu[1] = fr * a01; pu[2] = -(fr * (a00 * xp + a01 * yp));
+            pv[0] = gr * a01; pv[1] = gr * a11; pv[2] = -(gr * (a01 * xp + a11 * yp));
         }
         return st;
     }
@@ -855,12 +862,14 @@ struct KannalaBrandt {
             jv[4] = fyr * theta3; jv[5] = fyr * theta5; jv[6] = fyr * theta7; jv[7] = fyr * theta9;
         }
         if (PJ) {
+            T* const pu = ju + (WJ ? P : 0);  // beside the parameter Jacobian when both
+            T* const pv = jv + (WJ ? P : 0);
             if (axis) {
                 // x_r = y_r = 0 here (u = cx, v = cy): the finite limit of the
                 // off-axis block as r -> 0, theta_d / r -> 1 / z
                 const T iz = T(1) / z;
-                ju[0] = fx * iz; ju[1] = T(0); ju[2] = T(0);
-                jv[0] = T(0); jv[1] = fy * iz; jv[2] = T(0);
+                pu[0] = fx * iz; pu[1] = T(0); pu[2] = T(0);
+                pv[0] = T(0); pv[1] = fy * iz; pv[2] = T(0);
             } else {
                 // theta = atan2(r, z): d theta / dr = z / |p|^2, d theta / dz =
                 // -r / |p|^2; D = d theta_d / d theta.  With A = D z / |p|^2
@@ -874,8 +883,8 @@ struct KannalaBrandt {
                             T(7) * k3 * (theta3 * theta3) + T(9) * k4 * (theta5 * theta3);
                 const T A = D * z * in2, B = theta_d * irr, C = D * r * in2;
                 const T xx = x_r * x_r, yy = y_r * y_r, xy = x_r * y_r * (A - B);
-                ju[0] = fx * (A * xx + B * yy); ju[1] = fx * xy; ju[2] = -(fx * x_r * C);
-                jv[0] = fy * xy; jv[1] = fy * (A * yy + B * xx); jv[2] = -(fy * y_r * C);
+                pu[0] = fx * (A * xx + B * yy); pu[1] = fx * xy; pu[2] = -(fx * x_r * C);
+                pv[0] = fy * xy; pv[1] = fy * (A * yy + B * xx); pv[2] = -(fy * y_r * C);
             }
         }
         return st;
@@ -1297,13 +1306,15 @@ struct DoubleSphere {
             jv[4] = -tv * dda; jv[5] = -tv * ddx;
         }
         if (PJ) {
+            T* const pu = ju + (WJ ? P : 0);  // beside the parameter Jacobian when both
+            T* const pv = jv + (WJ ? P : 0);
             // d denom / d(x, y) = (x, y) kxy, d denom / dz = kz with
             // d gamma / d(x, y) = xi (x, y) / d1, d gamma / dz = xi z / d1 + 1
             const T xd1 = xi / d1, ad2 = alpha / d2;
             const T gz = xd1 * z + T(1);
             const T kxy = ad2 * (T(1) + gamma * xd1) + (T(1) - alpha) * xd1;
             const T kz = (ad2 * gamma + (T(1) - alpha)) * gz;
-            denom_point_jacobian(fx, fy, x, y, mx, my, FAST ? id : yd, kxy, kz, ju, jv);
+            denom_point_jacobian(fx, fy, x, y, mx, my, FAST ? id : yd, kxy, kz, pu, pv);
         }
         return ok ? ST_OK : ST_POINT_IS_OUT_SIDE_IMAGE;
     }
@@ -1368,9 +1379,11 @@ struct Ucm {
             jv[0] = T(0); jv[1] = my; jv[2] = T(0); jv[3] = T(1); jv[4] = -tv * dda;
         }
         if (PJ) {  // d denom / d(x, y) = alpha (x, y) / d, d denom / dz = alpha z / d + 1 - alpha
+            T* const pu = ju + (WJ ? P : 0);  // beside the parameter Jacobian when both
+            T* const pv = jv + (WJ ? P : 0);
             const T ad = alpha / d;
             denom_point_jacobian(fx, fy, x, y, mx, my, FAST ? id : yd, ad,
-                                 ad * z + (T(1) - alpha), ju, jv);
+                                 ad * z + (T(1) - alpha), pu, pv);
         }
         return ok ? ST_OK : ST_POINT_IS_OUT_SIDE_IMAGE;
     }
@@ -1440,9 +1453,11 @@ struct Eucm {
             jv[4] = -tv * dda; jv[5] = -tv * ddb;
         }
         if (PJ) {  // d denom / d(x, y) = alpha beta (x, y) / d, d denom / dz = alpha z / d + 1 - alpha
+            T* const pu = ju + (WJ ? P : 0);  // beside the parameter Jacobian when both
+            T* const pv = jv + (WJ ? P : 0);
             const T ad = alpha / d;
             denom_point_jacobian(fx, fy, x, y, mx, my, FAST ? id : yd, ad * beta,
-                                 ad * z + (T(1) - alpha), ju, jv);
+                                 ad * z + (T(1) - alpha), pu, pv);
         }
         return ok ? ST_OK : ST_POINT_IS_OUT_SIDE_IMAGE;
     }
@@ -1506,9 +1521,11 @@ struct Fov {
             jv[0] = T(0); jv[1] = my; jv[2] = T(0); jv[3] = T(1); jv[4] = fy * y * drd;
         }
         if (PJ) {
+            T* const pu = ju + (WJ ? P : 0);  // beside the parameter Jacobian when both
+            T* const pv = jv + (WJ ? P : 0);
             if (axis) {  // rd is the constant 2 tan(w/2) / w in this branch
-                ju[0] = fx * rd; ju[1] = T(0); ju[2] = T(0);
-                jv[0] = T(0); jv[1] = fy * rd; jv[2] = T(0);
+                pu[0] = fx * rd; pu[1] = T(0); pu[2] = T(0);
+                pv[0] = T(0); pv[1] = fy * rd; pv[2] = T(0);
             } else {
                 // rd = atan2(a, z) / (r w), a = 2 tan(w/2) r:
                 //   d rd / dr = (2 tan(w/2) z / (a^2 + z^2)) / (r w) - rd / r
@@ -1517,8 +1534,8 @@ struct Fov {
                 const T a = T(2) * tan_w_half * r;
                 const T tw = T(2) * tan_w_half / (wf * (a * a + z * z));
                 const T g = (tw * z - rd) / r2;  // (d rd / dr) / r
-                ju[0] = fx * (rd + x * x * g); ju[1] = fx * (x * y * g); ju[2] = -(fx * x * tw);
-                jv[0] = fy * (x * y * g); jv[1] = fy * (rd + y * y * g); jv[2] = -(fy * y * tw);
+                pu[0] = fx * (rd + x * x * g); pu[1] = fx * (x * y * g); pu[2] = -(fx * x * tw);
+                pv[0] = fy * (x * y * g); pv[1] = fy * (rd + y * y * g); pv[2] = -(fy * y * tw);
             }
         }
         return z < T(kEpsSqrt) ? ST_POINT_AT_CAMERA_CENTER : ST_OK;

@@ -676,6 +676,112 @@ ACM_API int acm_pose_optimize_batch(const acm_camera *cam, size_t n_views, acm_p
                                     double *information, void *workspace,
                                     size_t workspace_bytes, void *stream);
 
+/* Multi-view calibration: the intrinsics and every view's pose in one
+ * Levenberg-Marquardt.  K views of known world points, rough poses (device,
+ * in/out) and rough intrinsics (cam, host, in/out); the unknowns are the P
+ * parameters of the model that are not in fixed_mask, shared by all views,
+ * and a 6-DoF pose per view: minimise 0.5 sum ||project_theta(R_k X + t_k) -
+ * uv||^2 over theta and the poses.
+ *
+ * Observations are CSR by view exactly as acm_pose_optimize_batch takes them
+ * (view_offsets clamped into [0, n_observations], the same validity rule: a
+ * finite pixel, an index in [0, n_points), a finite world point, and an Ok
+ * fast projection at the state being evaluated; everything else is skipped,
+ * never dereferenced and no error).  A view with fewer than 3 valid
+ * observations at the start is ACM_POSE_TOO_FEW_OBSERVATIONS: its pose is
+ * left bit for bit, it contributes nothing and is not counted in
+ * summary->n_views_used.  No participating view: ACM_LM_FAILED, cam
+ * untouched.
+ *
+ * Per observation the Jacobian row pair is [Jp [I | -[p]x] | Jtheta]: the
+ * pose perturbation and retraction are acm_pose_optimize_batch's (left delta
+ * = (rho, phi), in double on the device).  The Hessian is an arrow -- K
+ * 6 x 6 pose blocks App_k, the P x P block Att and K couplings Atp_k -- and
+ * the loop is acm_lm_optimize's state machine on the FULL system, solved
+ * through the Schur complement: Marquardt damping A_jj + mu max(A_jj, 1e-12
+ * max(dmax, 1)) on every diagonal entry (dmax the largest diagonal entry of
+ * the whole system at the first evaluation), L_k = chol(App_k + damping), S =
+ * (Att + damping) - sum_k Atp_k App_k^-1 Apt_k and the matching g, summed
+ * over the views in view order, dtheta from a Cholesky of S over the free
+ * parameters, xn = clamp(x + dtheta), h = xn - x, and per view delta_k =
+ * -App_k^-1 (gp_k + Apt_k h).  When the clamp stops a parameter, that
+ * parameter is held at its clamped step and S is solved again for the others
+ * (the plain projection of a coupled step stalls: DESIGN.md section 8.4);
+ * without active bounds nothing changes.  A failed Cholesky in any view block or in S
+ * raises mu without an evaluation.  The predicted reduction -(g.h + 0.5 h^T A
+ * h) is over the full step with the undamped A; the gain-ratio (Nielsen)
+ * update, the three tolerances and the mu > 1e32 failure are
+ * acm_lm_optimize's, with the full step's norm against the intrinsics' norm
+ * in the parameter test (poses are local: their coordinates are 0).  A trial
+ * whose total n_valid is below the current one's is rejected
+ * (acm_triangulate's rule).  summary->evaluations counts the evaluations the
+ * state machine consumed; a step that ends the run by the parameter
+ * tolerance is not among them.
+ *
+ * Outputs: cam->params and poses receive the best accepted state;
+ * max_iterations = 0 leaves both bit for bit and fills every other output at
+ * the start.  view_status (device, required): ACM_POSE_TOO_FEW_OBSERVATIONS,
+ * or for every participating view ACM_POSE_OK when a tolerance ended the run
+ * (or max_iterations = 0) and ACM_POSE_NOT_CONVERGED otherwise.  When
+ * non-NULL (device): view_cost (0.5 sum ||r||^2 of the view; NaN for a
+ * TOO_FEW view), view_n_valid, and view_system, 256 doubles per view: the
+ * 16 x 16 Gram matrix M^T M of the view's augmented Jacobian M = [Jrho Jphi |
+ * Jtheta | 0 ... | r] at the returned state -- columns 0-5 the pose, 6 .. 5 +
+ * P the intrinsics (every parameter, fixed ones too), column 15 the residual,
+ * so [i][15] = (J^T r)_i and [15][15] = r.r; row-major, both triangles,
+ * padding exactly 0.  summary (host): information is the undamped reduced S
+ * at the returned state, P x P row-major, rows and columns of fixed
+ * parameters zero (all zero when a view's undamped pose block is singular).
+ *
+ * One 256-lane workgroup per view evaluates a state: acm_pose_optimize_batch's
+ * staging (views above ACM_POSE_BATCH_STAGE_OBSERVATIONS read global memory
+ * at every evaluation, same arithmetic and order), each lane's two rows of M
+ * through an LDS tile into v_mfma_f64_16x16x4_f64 rank-4 updates, in a fixed
+ * order: repeated calls return the same bits, and inserting a TOO_FEW view
+ * anywhere changes no other output bit.  Per iteration: five small launches
+ * and two small device-to-host copies, whatever n_views; poses never leave
+ * the device.
+ *
+ * Errors: acm_pose_optimize_batch's list (summary may be NULL), and
+ * fixed_mask bits >= P or has_bounds with lower[j] > upper[j] (or a NaN
+ * bound): ACM_ERR_INVALID_ARGUMENT.  n_views = 0 is valid and touches
+ * nothing.  The call synchronises the stream, as acm_lm_optimize does; no
+ * allocation, reentrant. */
+typedef struct acm_calibrate_config {
+    int32_t max_iterations;      /* default 50; 0 = evaluate only */
+    int32_t flags;               /* must be 0 */
+    double cost_tolerance;       /* defaults of acm_lm_default_config: 1e-6 */
+    double parameter_tolerance;  /* 1e-8 */
+    double gradient_tolerance;   /* 1e-6 */
+    double initial_damping;      /* 1e-4 */
+    uint32_t fixed_mask;         /* bit j set: intrinsic j is held at its start value */
+    uint32_t has_bounds;         /* bounds on the intrinsics only, as acm_lm_config */
+    double lower[ACM_MAX_PARAMS];
+    double upper[ACM_MAX_PARAMS];
+} acm_calibrate_config;
+
+typedef struct acm_calibrate_summary {
+    int32_t iterations;
+    int32_t termination; /* ACM_LM_* */
+    int32_t evaluations;
+    int32_t n_views_used;
+    double initial_cost;
+    double final_cost;
+    double n_valid;
+    double information[ACM_MAX_PARAMS * ACM_MAX_PARAMS];
+} acm_calibrate_summary;
+
+ACM_API void acm_calibrate_default_config(acm_calibrate_config *cfg);
+ACM_API size_t acm_calibrate_workspace_size(int model, size_t n_views, size_t n_observations);
+ACM_API int acm_calibrate(acm_camera *cam, size_t n_views, acm_pose *poses,
+                          size_t n_points, const double *points_world,
+                          const int64_t *view_offsets, size_t n_observations,
+                          const int32_t *obs_point, const double *obs_uv,
+                          const acm_calibrate_config *cfg, acm_calibrate_summary *summary,
+                          uint8_t *view_status, double *view_cost, uint32_t *view_n_valid,
+                          double *view_system, void *workspace, size_t workspace_bytes,
+                          void *stream);
+
 /* (r06) The sharded conversion's collectives.  One
  * process per GPU, each holding a shard of the correspondences; both
  * collectives are stream-ordered on device f64 buffers:
