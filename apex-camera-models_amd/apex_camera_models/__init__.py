@@ -19,6 +19,8 @@ from .optimizer import (CalibrationConfig, CalibrationResult, Pose, PoseBatchCon
                         PoseBatchResult, TriangulationConfig, calibrate,
                         TriangulationResult, alternate_bundle_adjustment, refine_pose,
                         refine_poses, tracks_by_view, tracks_from_dense, triangulate)
+from .optimizer import (PoseEstimateConfig, PoseEstimateResult, estimate_poses,  # noqa: E402
+                        p3p)
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
@@ -28,4 +30,5 @@ __all__ = [
     "TriangulationConfig", "TriangulationResult", "PoseBatchConfig", "PoseBatchResult",
     "CalibrationConfig", "CalibrationResult", "calibrate",
     "refine_poses", "tracks_by_view", "alternate_bundle_adjustment",
+    "PoseEstimateConfig", "PoseEstimateResult", "estimate_poses", "p3p",
 ]

@@ -131,6 +131,23 @@ POSE_OK, POSE_TOO_FEW_OBSERVATIONS, POSE_NOT_CONVERGED = 0, 1, 2
 POSE_BATCH_STAGE_OBSERVATIONS = 1024
 
 
+class PoseEstimateConfig(ctypes.Structure):
+    """acm_pose_estimate_config (include/acm.h)."""
+    _fields_ = [
+        ("n_hypotheses", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("inlier_angle", ctypes.c_double),
+        ("min_inliers", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+# acm_pose_est_status / the per-view LDS staging budget (include/acm.h)
+POSE_EST_OK, POSE_EST_TOO_FEW_OBSERVATIONS, POSE_EST_NO_MODEL = 0, 1, 2
+POSE_EST_STAGE_OBSERVATIONS = 1024
+
+
 class CalibrateConfig(ctypes.Structure):
     """acm_calibrate_config (include/acm.h)."""
     _fields_ = [
@@ -249,6 +266,10 @@ EXPORTED_SYMBOLS = (
     "acm_pose_optimize_batch_default_config",
     "acm_pose_optimize_batch_workspace_size",
     "acm_pose_optimize_batch",
+    "acm_p3p",
+    "acm_pose_estimate_batch_default_config",
+    "acm_pose_estimate_batch_workspace_size",
+    "acm_pose_estimate_batch",
     "acm_calibrate_default_config",
     "acm_calibrate_workspace_size",
     "acm_calibrate",
@@ -445,6 +466,16 @@ def load():
     L.acm_pose_optimize_batch.argtypes = [cam_p, sz, vp, sz, vp, vp, sz, vp, vp, pb_p, vp, vp, vp,
                                           vp, vp, vp, sz, vp]
     L.acm_pose_optimize_batch.restype = i
+    L.acm_p3p.argtypes = [sz, vp, vp, vp, vp, vp]
+    L.acm_p3p.restype = i
+    pe_p = ctypes.POINTER(PoseEstimateConfig)
+    L.acm_pose_estimate_batch_default_config.argtypes = [pe_p]
+    L.acm_pose_estimate_batch_default_config.restype = None
+    L.acm_pose_estimate_batch_workspace_size.argtypes = [sz, sz]
+    L.acm_pose_estimate_batch_workspace_size.restype = sz
+    L.acm_pose_estimate_batch.argtypes = [cam_p, sz, vp, sz, vp, vp, sz, vp, vp, pe_p, vp, vp, vp,
+                                          vp, vp, sz, vp]
+    L.acm_pose_estimate_batch.restype = i
     cal_p = ctypes.POINTER(CalibrateConfig)
     L.acm_calibrate_default_config.argtypes = [cal_p]
     L.acm_calibrate_default_config.restype = None

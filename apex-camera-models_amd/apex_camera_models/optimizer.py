@@ -473,6 +473,99 @@ def alternate_bundle_adjustment(model: CameraModel, poses, track_offsets, obs_vi
     return pt, tri, costs
 
 
+# ------------------------------------------------ absolute pose from scratch
+def p3p(bearings, points_world):
+    """The minimal absolute-pose solver (acm_p3p), batched: bearings (N, 3, 3)
+    -- f1, f2, f3 per triplet, any length -- and points_world (N, 3, 3).
+    Returns (poses (N, 4, 12) f64 -- R row-major, then t; NaN beyond the count
+    --, count (N,) u8) on the device."""
+    L = _lib.load()
+    f = _as_device_f64(torch.as_tensor(bearings).reshape(-1, 3), 3)
+    x = _as_device_f64(torch.as_tensor(points_world).reshape(-1, 3), 3)
+    if f.shape[0] % 3 or f.shape[0] != x.shape[0]:
+        raise ValueError("bearings and points_world must both be (N, 3, 3)")
+    n = f.shape[0] // 3
+    poses = torch.empty((n, 4, 12), dtype=torch.float64, device="cuda")
+    count = torch.empty((n,), dtype=torch.uint8, device="cuda")
+    _lib.check(L.acm_p3p(n, f.data_ptr() if n else None, x.data_ptr() if n else None,
+                         poses.data_ptr() if n else None, count.data_ptr() if n else None,
+                         _stream_handle()))
+    return poses, count
+
+
+@dataclass
+class PoseEstimateConfig:
+    """acm_pose_estimate_config; the defaults are
+    acm_pose_estimate_batch_default_config's, except inlier_angle: None takes
+    the angle of estimate_poses' threshold_px."""
+    n_hypotheses: int = 256
+    seed: int = 1
+    inlier_angle: Optional[float] = None
+    min_inliers: int = 4
+
+
+@dataclass
+class PoseEstimateResult:
+    """Device tensors: poses (K, 12) f64 (R row-major, then t; NaN where
+    status is not POSE_EST_OK), status (K,) u8 (_lib.POSE_EST_OK /
+    POSE_EST_TOO_FEW_OBSERVATIONS / POSE_EST_NO_MODEL), n_inliers (K,) i32,
+    n_usable (K,) i32, inlier_mask (M,) u8, one byte per observation."""
+    poses: torch.Tensor
+    status: torch.Tensor
+    n_inliers: torch.Tensor
+    n_usable: torch.Tensor
+    inlier_mask: torch.Tensor
+
+
+def estimate_poses(model: CameraModel, points_world, view_offsets, obs_point, obs_uv,
+                   config: Optional[PoseEstimateConfig] = None, threshold_px: float = 3.0,
+                   refine: bool = False,
+                   refine_config: Optional[PoseBatchConfig] = None) -> PoseEstimateResult:
+    """Every view's pose from 2-D / 3-D correspondences with no prior
+    (acm_pose_estimate_batch): P3P on the unprojected rays inside RANSAC, one
+    workgroup per view, all views in one launch.  Inputs as refine_poses
+    without start poses (tracks_by_view's output feeds the call unchanged).
+    Without config.inlier_angle the threshold is atan(threshold_px / min(fx,
+    fy)).  refine: refine_poses from the estimated poses over the inliers only
+    (the other observations get point index -1, one torch.where on the
+    device); the views whose status is not POSE_EST_OK stay as they are."""
+    import math
+    L = _lib.load()
+    pw = _as_device_f64(points_world, 3)
+    offs = torch.as_tensor(view_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    idx = torch.as_tensor(obs_point).to(device="cuda", dtype=torch.int32).contiguous()
+    uv = _as_device_f64(obs_uv, 2)
+    k, n, m = offs.shape[0] - 1, pw.shape[0], idx.shape[0]
+    if k < 0 or uv.shape[0] != m:
+        raise ValueError("view_offsets needs K + 1 entries; obs_point and obs_uv one row per observation")
+    cam = model.acm_camera()
+    c = config or PoseEstimateConfig()
+    cfg = _lib.PoseEstimateConfig()
+    L.acm_pose_estimate_batch_default_config(ctypes.byref(cfg))
+    cfg.n_hypotheses = c.n_hypotheses
+    cfg.seed = c.seed
+    cfg.min_inliers = c.min_inliers
+    cfg.inlier_angle = (c.inlier_angle if c.inlier_angle is not None
+                        else math.atan(threshold_px / min(cam.params[0], cam.params[1])))
+    poses = torch.empty((k, 12), dtype=torch.float64, device="cuda")
+    status = torch.empty((k,), dtype=torch.uint8, device="cuda")
+    n_inliers = torch.empty((k,), dtype=torch.int32, device="cuda")
+    n_usable = torch.empty((k,), dtype=torch.int32, device="cuda")
+    mask = torch.zeros((m,), dtype=torch.uint8, device="cuda")  # entries no view owns stay 0
+    ws_bytes = L.acm_pose_estimate_batch_workspace_size(k, m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device="cuda")
+    _lib.check(L.acm_pose_estimate_batch(
+        ctypes.byref(cam), k, poses.data_ptr() if k else None, n, pw.data_ptr() if n else None,
+        offs.data_ptr(), m, idx.data_ptr() if m else None, uv.data_ptr() if m else None,
+        ctypes.byref(cfg), status.data_ptr() if k else None, n_inliers.data_ptr() if k else None,
+        mask.data_ptr() if m else None, n_usable.data_ptr() if k else None, ws.data_ptr(),
+        ws_bytes, _stream_handle()))
+    if refine and k:
+        kept = torch.where(mask != 0, idx, torch.full_like(idx, -1))
+        poses = refine_poses(model, poses, pw, offs, kept, uv, refine_config).poses
+    return PoseEstimateResult(poses, status, n_inliers, n_usable, mask)
+
+
 # ------------------------------------------------------ multi-view calibration
 @dataclass
 class CalibrationConfig:

@@ -33,6 +33,7 @@
 #include "camera_models.hpp"
 #include "lm_core.hpp"
 #include "lm_doorbell.hpp"
+#include "p3p.hpp"
 
 namespace acm {
 
@@ -2270,6 +2271,327 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
         par ^= 1;
         pose_retract_dev(cur, h, ev);
     }
+}
+
+// ------------------------------------------- absolute pose from scratch
+// acm_p3p: one lane per triplet, p3p.hpp's solver (registers only).
+__global__ __launch_bounds__(kBlock) void k_p3p(size_t n, const double* __restrict__ bearings,
+                                                const double* __restrict__ points,
+                                                acm_pose* __restrict__ poses,
+                                                uint8_t* __restrict__ count) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double f[9], X[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        f[k] = bearings[9 * i + k];
+        X[k] = points[9 * i + k];
+    }
+    double* dst = reinterpret_cast<double*>(poses + 4 * i);
+    int m = 0;
+    if (p3p::normalize(f)) {
+        double S[4][3];
+        const unsigned mask = p3p::depths(f, X, S);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!(mask >> k & 1u)) continue;
+            double out[12];
+            if (!p3p::pose(f, X, S[k], out)) continue;
+#pragma unroll
+            for (int q = 0; q < 12; ++q) dst[12 * m + q] = out[q];
+            ++m;
+        }
+    }
+    const double qnan = __builtin_nan("");
+    for (int q = 12 * m; q < 48; ++q) dst[q] = qnan;
+    count[i] = (uint8_t)m;
+}
+
+// acm_pose_estimate_batch: RANSAC over P3P, one workgroup per view.  The
+// view's records (gathered world point and the unit bearing of the pixel, 48
+// B; X = NaN marks an unusable observation) are built once -- in LDS when the
+// view has at most kPoseEstStageObs observations, in the workspace (six
+// planes of n_obs doubles, the view's own range) otherwise -- so the Newton
+// unprojections run once per observation.  Lane l takes hypotheses l, l +
+// 256, ...: the sample, p3p.hpp, and per solution one pass over all records
+// (every lane reads the same record: a broadcast).  A lane keeps its best key
+// (count, score, h, solution); the keys are all different, so the workgroup's
+// minimum under the total order is the same whatever the order of the tree.
+constexpr int kPoseEstStageObs = ACM_POSE_EST_STAGE_OBSERVATIONS;  // per view; 48 B each
+
+struct PoseEstArgs {
+    size_t n_points, n_obs;
+    acm_pose* poses;
+    const double* X;
+    const int64_t* offs;
+    const int32_t* pt;
+    const double* uv;
+    uint8_t* status;
+    uint32_t* n_inliers;
+    uint8_t* mask;
+    uint32_t* n_usable;
+    double* ws;  // six planes of n_obs doubles
+    int H, min_inliers;
+    unsigned long long seed;
+    double cos2;
+};
+
+__device__ __forceinline__ unsigned long long pose_est_mix(unsigned long long z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// the inlier rule at pose P for the record (X, Y, Z, f): the angle between f
+// and R X + t is at most the threshold; e = 1 - cos^2 of it
+__device__ __forceinline__ bool pose_est_inlier(const double (&P)[12], double X, double Y, double Z,
+                                                double fx, double fy, double fz, double cos2,
+                                                double& e) {
+    const double px = P[0] * X + P[1] * Y + P[2] * Z + P[9];
+    const double py = P[3] * X + P[4] * Y + P[5] * Z + P[10];
+    const double pz = P[6] * X + P[7] * Y + P[8] * Z + P[11];
+    const double d = fx * px + fy * py + fz * pz;
+    const double pp = px * px + py * py + pz * pz;
+    if (!(d > 0.0 && d * d >= cos2 * pp)) return false;
+    e = 1.0 - d * d / pp;
+    return true;
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void pose_estimate_view(const PoseEstArgs& a, size_t view, long long ob,
+                                                   long long cnt, unsigned usable,
+                                                   const double* __restrict__ rec, size_t stride,
+                                                   int (&s_cnt)[kBlock], double (&s_sum)[kBlock],
+                                                   int (&s_hs)[kBlock][2], int (&s_lane)[kBlock],
+                                                   double (&s_pose)[12]) {
+    const double qnan = __builtin_nan("");
+    const int tid = threadIdx.x;
+    double* dst = reinterpret_cast<double*>(a.poses + view);
+    if (usable < 4u) {
+        if (tid < 12) dst[tid] = qnan;
+        if (tid == 0) {
+            a.status[view] = ACM_POSE_EST_TOO_FEW_OBSERVATIONS;
+            a.n_inliers[view] = 0;
+        }
+        if (a.mask)
+            for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
+        return;
+    }
+    // the lane's best: count (-1: no model), score, hypothesis, solution, pose
+    int bc = -1, bh = 0, bs = 0;
+    double bsum = 0.0, bp[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) bp[k] = qnan;
+    for (int h = tid; h < a.H; h += kBlock) {
+        long long i0 = -1, i1 = -1, i2 = -1;
+        int got = 0;
+        for (int d = 0; d < 8 && got < 3; ++d) {
+            const unsigned long long ctr = 8ull * (unsigned long long)h + (unsigned long long)d + 1ull;
+            const unsigned long long r = pose_est_mix(a.seed + ctr * 0x9E3779B97F4A7C15ull);
+            const long long j = (long long)__umul64hi(r, (unsigned long long)cnt);
+            if (!__builtin_isfinite(rec[j]) || j == i0 || j == i1) continue;
+            if (got == 0) i0 = j;
+            else if (got == 1) i1 = j;
+            else i2 = j;
+            ++got;
+        }
+        if (got < 3) continue;
+        double f[9], X[9];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            X[k] = rec[k * stride + i0];
+            X[3 + k] = rec[k * stride + i1];
+            X[6 + k] = rec[k * stride + i2];
+            f[k] = rec[(3 + k) * stride + i0];
+            f[3 + k] = rec[(3 + k) * stride + i1];
+            f[6 + k] = rec[(3 + k) * stride + i2];
+        }
+        double S[4][3];
+        const unsigned mask = p3p::depths(f, X, S);
+        int si = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (!(mask >> k & 1u)) continue;
+            double P[12];
+            if (!p3p::pose(f, X, S[k], P)) continue;
+            int c = 0;
+            double sum = 0.0;
+            for (long long j = 0; j < cnt; ++j) {
+                const double Xj = rec[j];
+                if (!__builtin_isfinite(Xj)) continue;
+                double e;
+                if (pose_est_inlier(P, Xj, rec[stride + j], rec[2 * stride + j], rec[3 * stride + j],
+                                    rec[4 * stride + j], rec[5 * stride + j], a.cos2, e)) {
+                    ++c;
+                    sum += e;
+                }
+            }
+            // h and the solution index only grow in a lane: a tie keeps the earlier
+            if (c > bc || (c == bc && sum < bsum)) {
+                bc = c;
+                bsum = sum;
+                bh = h;
+                bs = si;
+#pragma unroll
+                for (int q = 0; q < 12; ++q) bp[q] = P[q];
+            }
+            ++si;
+        }
+    }
+    s_cnt[tid] = bc;
+    s_sum[tid] = bsum;
+    s_hs[tid][0] = bh;
+    s_hs[tid][1] = bs;
+    s_lane[tid] = tid;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            const int o = tid + off;
+            const int c0 = s_cnt[tid], c1 = s_cnt[o];
+            const double u0 = s_sum[tid], u1 = s_sum[o];
+            const int h0 = s_hs[tid][0], h1 = s_hs[o][0], k0 = s_hs[tid][1], k1 = s_hs[o][1];
+            const bool take = c1 > c0 ||
+                              (c1 == c0 && c1 >= 0 &&
+                               (u1 < u0 || (u1 == u0 && (h1 < h0 || (h1 == h0 && k1 < k0)))));
+            if (take) {
+                s_cnt[tid] = c1;
+                s_sum[tid] = u1;
+                s_hs[tid][0] = h1;
+                s_hs[tid][1] = k1;
+                s_lane[tid] = s_lane[o];
+            }
+        }
+        __syncthreads();
+    }
+    const int best = s_cnt[0], winner = s_lane[0];
+    if (best < a.min_inliers) {  // also no model at all: best = -1
+        if (tid < 12) dst[tid] = qnan;
+        if (tid == 0) {
+            a.status[view] = ACM_POSE_EST_NO_MODEL;
+            a.n_inliers[view] = best < 0 ? 0u : (uint32_t)best;
+        }
+        if (a.mask)
+            for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
+        return;
+    }
+    if (tid == winner) {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) s_pose[q] = bp[q];
+    }
+    __syncthreads();
+    double P[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) P[q] = s_pose[q];
+    if (tid < 12) dst[tid] = s_pose[tid];
+    if (tid == 0) {
+        a.status[view] = ACM_POSE_EST_OK;
+        a.n_inliers[view] = (uint32_t)best;
+    }
+    if (a.mask) {
+        for (long long j = tid; j < cnt; j += kBlock) {
+            const double Xj = rec[j];
+            double e;
+            const bool in = __builtin_isfinite(Xj) &&
+                            pose_est_inlier(P, Xj, rec[stride + j], rec[2 * stride + j],
+                                            rec[3 * stride + j], rec[4 * stride + j],
+                                            rec[5 * stride + j], a.cos2, e);
+            a.mask[ob + j] = in ? 1 : 0;
+        }
+    }
+}
+
+template <class TagT>
+__global__ __launch_bounds__(kBlock) void k_pose_estimate(CamArg cam, PoseEstArgs a) {
+    using M = typename TagT::template type<double>;
+    __shared__ double s_rec[6 * kPoseEstStageObs];  // planes X, Y, Z, fx, fy, fz
+    __shared__ double s_sum[kBlock];
+    __shared__ int s_cnt[kBlock];
+    __shared__ int s_hs[kBlock][2];
+    __shared__ int s_lane[kBlock];
+    __shared__ double s_pose[12];
+    __shared__ unsigned s_usable;
+    const Cam<double> c = make_cam<double>(cam);
+    const size_t view = blockIdx.x;
+    // the view's observations, clamped into [0, n_obs] (k_pose_batch)
+    const long long nobs = (long long)a.n_obs;
+    long long ob = a.offs[view], oe = a.offs[view + 1];
+    ob = ob < 0 ? 0 : (ob > nobs ? nobs : ob);
+    oe = oe < ob ? ob : (oe > nobs ? nobs : oe);
+    const long long cnt = oe - ob;
+    const bool staged = cnt <= (long long)kPoseEstStageObs;  // workgroup-uniform
+    const double qnan = __builtin_nan("");
+    if (threadIdx.x == 0) s_usable = 0u;
+    __syncthreads();
+    // the records: j < cnt <= n_obs - ob, so a workspace plane is never overrun
+    double* wrec = a.ws + ob;
+    const size_t wstride = a.n_obs;
+    unsigned mine = 0;
+    for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+        const int32_t pi = a.pt[ob + j];
+        const double u = a.uv[2 * (ob + j)], v = a.uv[2 * (ob + j) + 1];
+        double X = qnan, Y = qnan, Z = qnan, fx = qnan, fy = qnan, fz = qnan;
+        if (pi >= 0 && (size_t)pi < a.n_points && __builtin_isfinite(u) && __builtin_isfinite(v)) {
+            const double wx = a.X[3 * (size_t)pi], wy = a.X[3 * (size_t)pi + 1],
+                         wz = a.X[3 * (size_t)pi + 2];
+            double rx, ry, rz;
+            if (__builtin_isfinite(wx) && __builtin_isfinite(wy) && __builtin_isfinite(wz) &&
+                M::unproject(c, u, v, rx, ry, rz) == ST_OK) {
+                if constexpr (std::is_same<TagT, Tag<Ucm>>::value) {
+                    // Ucm::unproject keeps the reference's denom = 1 - r^2, so
+                    // its ray is not the one that projects to (u, v) (off by up
+                    // to 1.5e-2 rad): a pose cannot be fitted to such bearings.
+                    // The status above decides usability as for every model;
+                    // the bearing is the projection's inverse, denom = 1 + r^2.
+                    const double gamma = 1.0 - c.p[4], xi = c.uk[0];  // xi = alpha / gamma
+                    const double mx = (u - c.p[2]) / c.p[0] * gamma, my = (v - c.p[3]) / c.p[1] * gamma;
+                    const double r2 = mx * mx + my * my;
+                    const double coeff = (xi + sqrt(1.0 + (1.0 - xi * xi) * r2)) / (1.0 + r2);
+                    rx = coeff * mx;
+                    ry = coeff * my;
+                    rz = coeff - xi;
+                }
+                const double nr = sqrt(rx * rx + ry * ry + rz * rz);
+                rx /= nr;
+                ry /= nr;
+                rz /= nr;
+                if (__builtin_isfinite(rx) && __builtin_isfinite(ry) && __builtin_isfinite(rz)) {
+                    X = wx;
+                    Y = wy;
+                    Z = wz;
+                    fx = rx;
+                    fy = ry;
+                    fz = rz;
+                    ++mine;
+                }
+            }
+        }
+        if (staged) {
+            s_rec[j] = X;
+            s_rec[kPoseEstStageObs + j] = Y;
+            s_rec[2 * kPoseEstStageObs + j] = Z;
+            s_rec[3 * kPoseEstStageObs + j] = fx;
+            s_rec[4 * kPoseEstStageObs + j] = fy;
+            s_rec[5 * kPoseEstStageObs + j] = fz;
+        } else {
+            wrec[j] = X;
+            wrec[wstride + j] = Y;
+            wrec[2 * wstride + j] = Z;
+            wrec[3 * wstride + j] = fx;
+            wrec[4 * wstride + j] = fy;
+            wrec[5 * wstride + j] = fz;
+        }
+    }
+    if (mine) atomicAdd(&s_usable, mine);
+    __threadfence_block();
+    __syncthreads();
+    const unsigned usable = s_usable;
+    if (threadIdx.x == 0 && a.n_usable) a.n_usable[view] = usable;
+    if (staged)
+        pose_estimate_view<true>(a, view, ob, cnt, usable, s_rec, (size_t)kPoseEstStageObs, s_cnt,
+                                 s_sum, s_hs, s_lane, s_pose);
+    else
+        pose_estimate_view<false>(a, view, ob, cnt, usable, wrec, wstride, s_cnt, s_sum, s_hs,
+                                  s_lane, s_pose);
 }
 
 // ------------------------------------------------------------ calibration
@@ -6659,6 +6981,86 @@ ACM_API int acm_pose_optimize_batch(const acm_camera* cam, size_t n_views, acm_p
         hipLaunchKernelGGL(k_pose_batch<TagT>, dim3((unsigned)n_views), dim3(kBlock), 0, s,
                            prep(*cam), a);
         return check_launch("acm_pose_optimize_batch");
+    });
+}
+
+ACM_API int acm_p3p(size_t n, const double* bearings, const double* points_world, acm_pose* poses,
+                    uint8_t* count, void* stream) {
+    if (n == 0) return ACM_SUCCESS;
+    if (!bearings || !points_world || !poses || !count)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (n > (size_t)0x7fffffff * kBlock)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many triplets for one launch");
+    const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_p3p, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, n, bearings,
+                       points_world, poses, count);
+    return check_launch("acm_p3p");
+}
+
+ACM_API void acm_pose_estimate_batch_default_config(acm_pose_estimate_config* cfg) {
+    if (!cfg) return;
+    cfg->n_hypotheses = 256;
+    cfg->flags = 0;
+    cfg->seed = 1;
+    cfg->inlier_angle = 5e-3;
+    cfg->min_inliers = 4;
+    cfg->reserved = 0;
+}
+
+// 64 reserved bytes, then the records of the views too long for LDS: six
+// planes of n_observations doubles (a view uses its own range of each plane)
+ACM_API size_t acm_pose_estimate_batch_workspace_size(size_t, size_t n_observations) {
+    return 64 + 48 * n_observations;
+}
+
+ACM_API int acm_pose_estimate_batch(const acm_camera* cam, size_t n_views, acm_pose* poses,
+                                    size_t n_points, const double* points_world,
+                                    const int64_t* view_offsets, size_t n_observations,
+                                    const int32_t* obs_point, const double* obs_uv,
+                                    const acm_pose_estimate_config* cfg, uint8_t* status,
+                                    uint32_t* n_inliers, uint8_t* inlier_mask, uint32_t* n_usable,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
+    if (cfg->n_hypotheses < 1 || cfg->n_hypotheses > 65536 || cfg->flags != 0 ||
+        !(cfg->inlier_angle > 0.0 && cfg->inlier_angle < kPi / 2.0) || cfg->min_inliers < 4)
+        return fail(ACM_ERR_INVALID_ARGUMENT,
+                    "n_hypotheses outside 1 .. 65536, nonzero flags, inlier_angle outside (0, pi/2) "
+                    "or min_inliers < 4");
+    if (n_views == 0) return ACM_SUCCESS;
+    if (!poses || !view_offsets || !status || !n_inliers || (n_points && !points_world) ||
+        (n_observations && (!obs_point || !obs_uv)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace ||
+        workspace_bytes < acm_pose_estimate_batch_workspace_size(n_views, n_observations))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "pose estimation workspace too small");
+    if (n_views > (size_t)0x7fffffff)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many views for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_model(cam->model, [&](auto tag) -> int {
+        using TagT = decltype(tag);
+        PoseEstArgs a;
+        a.n_points = n_points;
+        a.n_obs = n_observations;
+        a.poses = poses;
+        a.X = points_world;
+        a.offs = view_offsets;
+        a.pt = obs_point;
+        a.uv = obs_uv;
+        a.status = status;
+        a.n_inliers = n_inliers;
+        a.mask = inlier_mask;
+        a.n_usable = n_usable;
+        a.ws = reinterpret_cast<double*>(static_cast<char*>(workspace) + 64);
+        a.H = cfg->n_hypotheses;
+        a.min_inliers = cfg->min_inliers;
+        a.seed = cfg->seed;
+        const double ci = std::cos(cfg->inlier_angle);
+        a.cos2 = ci * ci;
+        hipLaunchKernelGGL(k_pose_estimate<TagT>, dim3((unsigned)n_views), dim3(kBlock), 0, s,
+                           prep(*cam, false, true), a);
+        return check_launch("acm_pose_estimate_batch");
     });
 }
 

@@ -676,6 +676,132 @@ ACM_API int acm_pose_optimize_batch(const acm_camera *cam, size_t n_views, acm_p
                                     double *information, void *workspace,
                                     size_t workspace_bytes, void *stream);
 
+/* Absolute pose from scratch: the minimal solver and RANSAC over it.  Every
+ * solver above is a local Levenberg-Marquardt that needs a start pose and
+ * takes every observation at face value; these two calls produce that start
+ * pose from raw 2-D / 3-D correspondences, and the set of observations that
+ * agree with it.  The camera models are mostly omnidirectional, so the solver
+ * works on bearing vectors (unprojected rays), not on normalised pixels.
+ *
+ * acm_p3p: n independent triplets, one lane each.  bearings: 9 n f64, triplet
+ * i holds f1, f2, f3 (they need not be unit; the call normalises them);
+ * points_world: 9 n f64, X1, X2, X3.  poses: 4 n acm_pose; count: n bytes.
+ * A solution is a pose (world -> camera, p = R X + t) for which R X_i + t is a
+ * positive multiple of f_i, i = 1, 2, 3.  All real solutions with positive
+ * depths are returned, count[i] in 0 .. 4 of them in poses[4 i ..], in the
+ * order of the quartic's roots below; the slots beyond count[i] are NaN.  R is
+ * a rotation (orthonormal to rounding, det +1) by construction.
+ *
+ * The route is Grunert's, in f64: with a = |X2 - X3|, b = |X1 - X3|, c =
+ * |X1 - X2| and the cosines of the angles between the bearings, a quartic in
+ * v = s3 / s1 (s_i the depths); the quartic (or, when its constant term is the
+ * larger, the one in 1 / v) is factored into two real quadratics through the
+ * largest real root of its resolvent cubic -- no eigen-solver -- and each real
+ * root takes two Newton steps on the quartic; u = s2 / s1 follows from a
+ * linear relation and s1 from the law of cosines; v <= 0 or u <= 0 is dropped.
+ * The depths then take three Gauss-Newton steps on the three law-of-cosines
+ * equations, and a solution is kept when its depths are positive and the
+ * three residuals are at most 1e-12 (a^2 + b^2 + c^2).  R, t align the
+ * orthonormal frame of (s_i f_i) -- first axis along the first edge, third
+ * the triangle's normal -- to the frame of (X_i), and the centroids.  A
+ * (numerically) double root of the quartic may be returned twice.
+ *
+ * count = 0: a non-finite input, a bearing without direction, collinear or
+ * repeated world points, or two parallel bearings (the sine of the angle at
+ * most 1e-10 in each case), or no real solution.  n = 0 is valid.  NULL
+ * buffers with n > 0: ACM_ERR_INVALID_ARGUMENT.  No workspace, stream-ordered,
+ * reentrant.
+ *
+ * acm_pose_estimate_batch: RANSAC over that solver, one 256-lane workgroup per
+ * view, all views in one launch.  The input is acm_pose_optimize_batch's (CSR
+ * by view, view_offsets clamped into [0, n_observations], one camera for all
+ * views) without start poses: poses is output only.
+ *
+ * An observation is usable iff its pixel is finite, obs_point[j] lies in
+ * [0, n_points), its world point is finite and the unprojection of the pixel
+ * (acm_unproject's default numerics, as acm_triangulate's midpoint start) is
+ * Ok with a finite direction; its bearing f is that ray, normalised.  One
+ * model differs: the UCM unprojection keeps the reference's denominator
+ * 1 - r^2, so its ray is not the one that projects to the pixel (off by up to
+ * 1.5e-2 rad on the sample camera) and no pose fits such bearings; for UCM
+ * that unprojection still decides Ok, and f is the projection's inverse, the
+ * same formula with 1 + r^2.
+ * Anything else is skipped -- an out-of-range index is never dereferenced and
+ * is no error of the call.  n_usable (nullable) receives the count per view.
+ * The view's records (X, Y, Z, fx, fy, fz; 48 B) are built once: in LDS for a
+ * view of at most ACM_POSE_EST_STAGE_OBSERVATIONS observations, in the
+ * workspace otherwise (the same arithmetic in the same order), so an
+ * iterative unprojection (KB, RadTan) runs once per observation, never per
+ * hypothesis.
+ *
+ * Hypothesis h = 0 .. n_hypotheses - 1 (lanes stride over h) draws local
+ * indices j = (splitmix64(seed + ctr 0x9E3779B97F4A7C15) cnt) >> 64 with ctr =
+ * 8 h + d + 1 for the draws d = 0 .. 7, cnt the view's (clamped) observation
+ * count, all in 64-bit wrapping arithmetic and splitmix64(z): z = (z ^ z >>
+ * 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) 0x94D049BB133111EB; z ^ z >> 31.
+ * The first three draws that are usable and pairwise distinct form the
+ * sample; if eight draws do not yield three the hypothesis is void.  The draw
+ * depends on seed, h and cnt only.  The sample goes through acm_p3p's solver,
+ * and each of its solutions is scored over all usable observations of the
+ * view in order: with p = R X + t, observation j is an inlier iff f.p > 0 and
+ * (f.p)^2 >= cos^2(inlier_angle) (p.p).  The key of a solution is (inlier
+ * count descending, sum over the inliers of 1 - (f.p)^2 / (p.p) ascending, h
+ * ascending, solution index ascending), a total order, so the winner does not
+ * depend on the order of the reduction.
+ *
+ * Outputs per view: the winner's pose, status (acm_pose_est_status, required),
+ * n_inliers (required), and when non-NULL inlier_mask (one byte per
+ * observation, 1 for the winner's inliers, 0 for every other entry of the
+ * view's clamped range, unusable observations included).  Fewer than 4 usable
+ * observations: ACM_POSE_EST_TOO_FEW_OBSERVATIONS, the pose all NaN, n_inliers
+ * = 0, the mask 0.  No hypothesis with a solution, or a best count below
+ * min_inliers: ACM_POSE_EST_NO_MODEL, the pose NaN, n_inliers = the best count
+ * (0 without a model), the mask 0.  Views whose clamped ranges overlap (which
+ * valid offsets never do) write the same mask bytes from several workgroups.
+ *
+ * A view's outputs depend only on its own observation list in order, the
+ * points it names, the camera and the config -- not on n_views, its index or
+ * the other views -- and repeated calls return the same bits.
+ *
+ * Errors: acm_pose_optimize_batch's list (n_inliers is required like status;
+ * workspace: device, 8-byte aligned, acm_pose_estimate_batch_workspace_size
+ * bytes), and ACM_ERR_INVALID_ARGUMENT for n_hypotheses outside 1 .. 65536,
+ * nonzero flags, inlier_angle outside (0, pi/2) or min_inliers < 4.  n_views =
+ * 0 is valid and touches nothing.  Stream-ordered, no allocation, no host
+ * synchronisation, reentrant (two calls in flight need two workspaces). */
+ACM_API int acm_p3p(size_t n, const double *bearings, const double *points_world,
+                    acm_pose *poses, uint8_t *count, void *stream);
+
+typedef enum acm_pose_est_status {
+    ACM_POSE_EST_OK = 0,
+    ACM_POSE_EST_TOO_FEW_OBSERVATIONS = 1, /* fewer than 4 usable observations */
+    ACM_POSE_EST_NO_MODEL = 2              /* no solution, or fewer than min_inliers inliers */
+} acm_pose_est_status;
+
+/* observations of one view whose records stay in LDS (48 B each); a longer
+ * view keeps them in the workspace */
+#define ACM_POSE_EST_STAGE_OBSERVATIONS 1024
+
+typedef struct acm_pose_estimate_config {
+    int32_t n_hypotheses;   /* default 256; 1 .. 65536 */
+    int32_t flags;          /* must be 0 */
+    uint64_t seed;          /* default 1 */
+    double inlier_angle;    /* radians, in (0, pi/2); default 5e-3 */
+    int32_t min_inliers;    /* default 4; >= 4 */
+    int32_t reserved;
+} acm_pose_estimate_config;
+
+ACM_API void acm_pose_estimate_batch_default_config(acm_pose_estimate_config *cfg);
+ACM_API size_t acm_pose_estimate_batch_workspace_size(size_t n_views, size_t n_observations);
+ACM_API int acm_pose_estimate_batch(const acm_camera *cam, size_t n_views, acm_pose *poses,
+                                    size_t n_points, const double *points_world,
+                                    const int64_t *view_offsets, size_t n_observations,
+                                    const int32_t *obs_point, const double *obs_uv,
+                                    const acm_pose_estimate_config *cfg, uint8_t *status,
+                                    uint32_t *n_inliers, uint8_t *inlier_mask,
+                                    uint32_t *n_usable, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
 /* Multi-view calibration: the intrinsics and every view's pose in one
  * Levenberg-Marquardt.  K views of known world points, rough poses (device,
  * in/out) and rough intrinsics (cam, host, in/out); the unknowns are the P
