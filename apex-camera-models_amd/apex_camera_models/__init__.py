@@ -21,6 +21,8 @@ from .optimizer import (CalibrationConfig, CalibrationResult, Pose, PoseBatchCon
                         refine_poses, tracks_by_view, tracks_from_dense, triangulate)
 from .optimizer import (PoseEstimateConfig, PoseEstimateResult, estimate_poses,  # noqa: E402
                         p3p)
+from .optimizer import (RelativePoseConfig, RelativePoseResult,  # noqa: E402
+                        estimate_relative_poses, relative_pose_8pt, two_view_tracks)
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
@@ -31,4 +33,6 @@ __all__ = [
     "CalibrationConfig", "CalibrationResult", "calibrate",
     "refine_poses", "tracks_by_view", "alternate_bundle_adjustment",
     "PoseEstimateConfig", "PoseEstimateResult", "estimate_poses", "p3p",
+    "RelativePoseConfig", "RelativePoseResult", "estimate_relative_poses", "relative_pose_8pt",
+    "two_view_tracks",
 ]

@@ -148,6 +148,23 @@ POSE_EST_OK, POSE_EST_TOO_FEW_OBSERVATIONS, POSE_EST_NO_MODEL = 0, 1, 2
 POSE_EST_STAGE_OBSERVATIONS = 1024
 
 
+class RelativePoseConfig(ctypes.Structure):
+    """acm_relative_pose_config (include/acm.h)."""
+    _fields_ = [
+        ("n_hypotheses", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("inlier_angle", ctypes.c_double),
+        ("min_inliers", ctypes.c_int32),
+        ("refit_rounds", ctypes.c_int32),
+    ]
+
+
+# acm_relpose_status / the per-pair LDS staging budget (include/acm.h)
+RELPOSE_OK, RELPOSE_TOO_FEW_MATCHES, RELPOSE_NO_MODEL = 0, 1, 2
+RELPOSE_STAGE_MATCHES = 1024
+
+
 class CalibrateConfig(ctypes.Structure):
     """acm_calibrate_config (include/acm.h)."""
     _fields_ = [
@@ -270,6 +287,10 @@ EXPORTED_SYMBOLS = (
     "acm_pose_estimate_batch_default_config",
     "acm_pose_estimate_batch_workspace_size",
     "acm_pose_estimate_batch",
+    "acm_relative_pose_8pt",
+    "acm_relative_pose_batch_default_config",
+    "acm_relative_pose_batch_workspace_size",
+    "acm_relative_pose_batch",
     "acm_calibrate_default_config",
     "acm_calibrate_workspace_size",
     "acm_calibrate",
@@ -476,7 +497,19 @@ def load():
     L.acm_pose_estimate_batch.argtypes = [cam_p, sz, vp, sz, vp, vp, sz, vp, vp, pe_p, vp, vp, vp,
                                           vp, vp, sz, vp]
     L.acm_pose_estimate_batch.restype = i
-    cal_p = ctypes.POINTER(CalibrateConfig)
+    L.acm_relative_pose_8pt.argtypes = [sz, vp, vp, vp, vp, vp, vp]
+    L.acm_relative_pose_8pt.restype = i
+    rp_p = ctypes.POINTER(RelativePoseConfig)
+    L.acm_relative_pose_batch_default_config.argtypes = [rp_p]
+    L.acm_relative_pose_batch_default_config.restype = None
+    L.acm_relative_pose_batch_workspace_size.argtypes = [sz, sz]
+    L.acm_relative_pose_batch_workspace_size.restype = sz
+    # cam, n_pairs, poses, pair_offsets, n_matches, uv_a, uv_b, cfg, status, n_inliers, mask,
+    # n_usable, workspace, workspace_bytes, stream
+    L.acm_relative_pose_batch.argtypes = [cam_p, sz, vp, vp, sz, vp, vp, rp_p, vp, vp, vp, vp, vp,
+                                          sz, vp]
+    L.acm_relative_pose_batch.restype = i
+    cal_p =ctypes.POINTER(CalibrateConfig)
     L.acm_calibrate_default_config.argtypes = [cal_p]
     L.acm_calibrate_default_config.restype = None
     L.acm_calibrate_workspace_size.argtypes = [i, sz, sz]

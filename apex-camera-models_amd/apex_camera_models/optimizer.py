@@ -566,6 +566,129 @@ def estimate_poses(model: CameraModel, points_world, view_offsets, obs_point, ob
     return PoseEstimateResult(poses, status, n_inliers, n_usable, mask)
 
 
+# --------------------------------------------------- two-view relative pose
+def relative_pose_8pt(bearings_a, bearings_b):
+    """The 8-point relative-pose solver (acm_relative_pose_8pt), batched:
+    bearings_a, bearings_b (N, 8, 3), the rays of eight matches in image A and
+    in image B, any length.  Returns (poses (N, 12) f64 -- p_b = R p_a + t, R
+    row-major, then the unit t --, essential (N, 9) f64 -- unit norm, signed
+    as [t]x R --, n_front (N,) u8) on the device; NaN and 0 where it fails."""
+    L = _lib.load()
+    fa = _as_device_f64(torch.as_tensor(bearings_a).reshape(-1, 3), 3)
+    fb = _as_device_f64(torch.as_tensor(bearings_b).reshape(-1, 3), 3)
+    if fa.shape[0] % 8 or fa.shape[0] != fb.shape[0]:
+        raise ValueError("bearings_a and bearings_b must both be (N, 8, 3)")
+    n = fa.shape[0] // 8
+    poses = torch.empty((n, 12), dtype=torch.float64, device="cuda")
+    ess = torch.empty((n, 9), dtype=torch.float64, device="cuda")
+    front = torch.empty((n,), dtype=torch.uint8, device="cuda")
+    _lib.check(L.acm_relative_pose_8pt(n, fa.data_ptr() if n else None, fb.data_ptr() if n else None,
+                                       poses.data_ptr() if n else None, ess.data_ptr() if n else None,
+                                       front.data_ptr() if n else None, _stream_handle()))
+    return poses, ess, front
+
+
+@dataclass
+class RelativePoseConfig:
+    """acm_relative_pose_config; the defaults are
+    acm_relative_pose_batch_default_config's, except inlier_angle: None takes
+    the angle of estimate_relative_poses' threshold_px."""
+    n_hypotheses: int = 512
+    seed: int = 1
+    inlier_angle: Optional[float] = None
+    min_inliers: int = 8
+    refit_rounds: int = 3
+
+
+@dataclass
+class RelativePoseResult:
+    """Device tensors: poses (K, 12) f64 (camera A -> camera B, R row-major,
+    then the unit t; NaN where status is not RELPOSE_OK), status (K,) u8
+    (_lib.RELPOSE_OK / RELPOSE_TOO_FEW_MATCHES / RELPOSE_NO_MODEL), n_inliers
+    (K,) i32, n_usable (K,) i32, inlier_mask (M,) u8, one byte per match."""
+    poses: torch.Tensor
+    status: torch.Tensor
+    n_inliers: torch.Tensor
+    n_usable: torch.Tensor
+    inlier_mask: torch.Tensor
+
+
+def estimate_relative_poses(model: CameraModel, pair_offsets, uv_a, uv_b,
+                            config: Optional[RelativePoseConfig] = None,
+                            threshold_px: float = 3.0) -> RelativePoseResult:
+    """Every view pair's relative pose from 2-D / 2-D matches alone
+    (acm_relative_pose_batch): the 8-point solver on the unprojected rays
+    inside RANSAC with a refit over the inliers, one workgroup per pair, all
+    pairs in one launch.  pair_offsets (K + 1,) int64: pair k owns the matches
+    pair_offsets[k] .. pair_offsets[k + 1] - 1; uv_a, uv_b (M, 2): their pixels
+    in image A and in image B of the pair.  Without config.inlier_angle the
+    threshold is atan(threshold_px / min(fx, fy))."""
+    import math
+    L = _lib.load()
+    offs = torch.as_tensor(pair_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    ua = _as_device_f64(uv_a, 2)
+    ub = _as_device_f64(uv_b, 2)
+    k, m = offs.shape[0] - 1, ua.shape[0]
+    if k < 0 or ub.shape[0] != m:
+        raise ValueError("pair_offsets needs K + 1 entries; uv_a and uv_b one row per match")
+    cam = model.acm_camera()
+    c = config or RelativePoseConfig()
+    cfg = _lib.RelativePoseConfig()
+    L.acm_relative_pose_batch_default_config(ctypes.byref(cfg))
+    cfg.n_hypotheses = c.n_hypotheses
+    cfg.seed = c.seed
+    cfg.min_inliers = c.min_inliers
+    cfg.refit_rounds = c.refit_rounds
+    cfg.inlier_angle = (c.inlier_angle if c.inlier_angle is not None
+                        else math.atan(threshold_px / min(cam.params[0], cam.params[1])))
+    poses = torch.empty((k, 12), dtype=torch.float64, device="cuda")
+    status = torch.empty((k,), dtype=torch.uint8, device="cuda")
+    n_inliers = torch.empty((k,), dtype=torch.int32, device="cuda")
+    n_usable = torch.empty((k,), dtype=torch.int32, device="cuda")
+    mask = torch.zeros((m,), dtype=torch.uint8, device="cuda")  # entries no pair owns stay 0
+    ws_bytes = L.acm_relative_pose_batch_workspace_size(k, m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device="cuda")
+    _lib.check(L.acm_relative_pose_batch(
+        ctypes.byref(cam), k, poses.data_ptr() if k else None, offs.data_ptr(), m,
+        ua.data_ptr() if m else None, ub.data_ptr() if m else None, ctypes.byref(cfg),
+        status.data_ptr() if k else None, n_inliers.data_ptr() if k else None,
+        mask.data_ptr() if m else None, n_usable.data_ptr() if k else None, ws.data_ptr(),
+        ws_bytes, _stream_handle()))
+    return RelativePoseResult(poses, status, n_inliers, n_usable, mask)
+
+
+def two_view_tracks(pair_offsets, uv_a, uv_b, inlier_mask, poses=None):
+    """estimate_relative_poses' inliers as triangulate's input, built on the
+    device without a loop over the pairs.  Pair k becomes the views 2 k (pose
+    [I | 0]) and 2 k + 1 (pose [R | t], row k of poses), and every inlier match
+    one track of two observations.  Returns (view_poses (2 K, 12) -- None
+    without poses --, track_offsets (N + 1,) int64, obs_view (2 N,) int32,
+    obs_uv (2 N, 2) f64, match (N,) int64: the match each track came from).
+    The points triangulate returns are in camera A's frame of their pair, in
+    units of the baseline."""
+    offs = torch.as_tensor(pair_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    ua = _as_device_f64(uv_a, 2)
+    ub = _as_device_f64(uv_b, 2)
+    mask = torch.as_tensor(inlier_mask).to(device="cuda")
+    if offs.shape[0] < 1 or ub.shape[0] != ua.shape[0] or mask.shape[0] != ua.shape[0]:
+        raise ValueError("pair_offsets needs K + 1 entries; uv_a, uv_b and inlier_mask one row per match")
+    k = offs.shape[0] - 1
+    match = torch.nonzero(mask != 0).reshape(-1)
+    n = match.shape[0]
+    pair = torch.bucketize(match, offs[1:].contiguous(), right=True)  # offs[p] <= match < offs[p + 1]
+    obs_view = torch.stack([2 * pair, 2 * pair + 1], dim=1).reshape(-1).to(torch.int32)
+    obs_uv = torch.stack([ua[match], ub[match]], dim=1).reshape(-1, 2).contiguous()
+    track_offsets = 2 * torch.arange(n + 1, dtype=torch.int64, device="cuda")
+    view_poses = None
+    if poses is not None:
+        rel = _poses_tensor(poses)
+        if rel.shape[0] != k:
+            raise ValueError("poses must have one row per pair")
+        eye = torch.tensor([1.0, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0], dtype=torch.float64, device="cuda")
+        view_poses = torch.stack([eye.expand(k, 12), rel], dim=1).reshape(2 * k, 12).contiguous()
+    return view_poses, track_offsets, obs_view, obs_uv, match
+
+
 # ------------------------------------------------------ multi-view calibration
 @dataclass
 class CalibrationConfig:

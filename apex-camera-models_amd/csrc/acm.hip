@@ -34,6 +34,7 @@
 #include "lm_core.hpp"
 #include "lm_doorbell.hpp"
 #include "p3p.hpp"
+#include "essential.hpp"
 
 namespace acm {
 
@@ -2592,6 +2593,439 @@ __global__ __launch_bounds__(kBlock) void k_pose_estimate(CamArg cam, PoseEstArg
     else
         pose_estimate_view<false>(a, view, ob, cnt, usable, wrec, wstride, s_cnt, s_sum, s_hs,
                                   s_lane, s_pose);
+}
+
+// -------------------------------------------------- two-view relative pose
+// acm_relative_pose_8pt: one lane per problem, essential.hpp's solver
+// (registers only).
+__global__ __launch_bounds__(kBlock) void k_relative_pose_8pt(size_t n,
+                                                              const double* __restrict__ fa,
+                                                              const double* __restrict__ fb,
+                                                              acm_pose* __restrict__ poses,
+                                                              double* __restrict__ essential,
+                                                              uint8_t* __restrict__ n_front) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double E[9];
+    const int front = essential::solve(8, fa + 24 * i, fb + 24 * i,
+                                       reinterpret_cast<double*>(poses + i), E);
+    if (essential) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) essential[9 * i + q] = E[q];
+    }
+    n_front[i] = (uint8_t)front;
+}
+
+// acm_relative_pose_batch: RANSAC over the 8-point solver, one workgroup per
+// view pair, laid out as k_pose_estimate: the pair's records (the unit
+// bearings of both pixels, 48 B; fa.x = NaN marks an unusable match) are built
+// once, in LDS or in the pair's own range of six workspace planes; lane l
+// takes hypotheses l, l + 256, ...; a lane keeps its best key (count, score,
+// h) and the workgroup's minimum under that total order wins.  The refit
+// rounds then run with the whole workgroup on one model (relpose_refit).
+constexpr int kRelPoseStage = ACM_RELPOSE_STAGE_MATCHES;  // per pair; 48 B each
+
+struct RelPoseArgs {
+    size_t n_matches;
+    acm_pose* poses;
+    const int64_t* offs;
+    const double* uv_a;
+    const double* uv_b;
+    uint8_t* status;
+    uint32_t* n_inliers;
+    uint8_t* mask;
+    uint32_t* n_usable;
+    double* ws;  // six planes of n_matches doubles
+    int H, min_inliers, refit_rounds;
+    unsigned long long seed;
+    double sin2;
+};
+
+// the eight local indices of a sample, in named fields: an array indexed by
+// the number of draws taken so far would leave the registers
+struct RelPoseSample {
+    long long j0 = -1, j1 = -1, j2 = -1, j3 = -1, j4 = -1, j5 = -1, j6 = -1, j7 = -1;
+    __device__ __forceinline__ bool has(long long j) const {
+        return j == j0 || j == j1 || j == j2 || j == j3 || j == j4 || j == j5 || j == j6 || j == j7;
+    }
+    __device__ __forceinline__ void set(int q, long long j) {
+        j0 = q == 0 ? j : j0;
+        j1 = q == 1 ? j : j1;
+        j2 = q == 2 ? j : j2;
+        j3 = q == 3 ? j : j3;
+        j4 = q == 4 ? j : j4;
+        j5 = q == 5 ? j : j5;
+        j6 = q == 6 ? j : j6;
+        j7 = q == 7 ? j : j7;
+    }
+    __device__ __forceinline__ long long get(int q) const {
+        return q == 0 ? j0 : q == 1 ? j1 : q == 2 ? j2 : q == 3 ? j3 : q == 4 ? j4 : q == 5 ? j5
+                                                                                : q == 6 ? j6 : j7;
+    }
+};
+
+// what the refit rounds share through LDS
+struct RelPoseShared {
+    double sum[kBlock];
+    int cnt[kBlock];
+    int h[kBlock];
+    int lane[kBlock];
+    double factor[kBlock / 64][essential::kTri];
+    double pose[12];
+    int front[4];
+    unsigned usable;
+};
+
+// The unit bearing of pixel (u, v): k_pose_estimate's rule, restated so that
+// kernel stays as it is -- the model's unprojection decides Ok, and for UCM
+// the bearing is the projection's inverse (denom = 1 + r^2).
+template <class TagT>
+__device__ __forceinline__ bool relpose_bearing(const Cam<double>& c, double u, double v, double& rx,
+                                                double& ry, double& rz) {
+    using M = typename TagT::template type<double>;
+    if (!(__builtin_isfinite(u) && __builtin_isfinite(v))) return false;
+    if (M::unproject(c, u, v, rx, ry, rz) != ST_OK) return false;
+    if constexpr (std::is_same<TagT, Tag<Ucm>>::value) {
+        const double gamma = 1.0 - c.p[4], xi = c.uk[0];  // xi = alpha / gamma
+        const double mx = (u - c.p[2]) / c.p[0] * gamma, my = (v - c.p[3]) / c.p[1] * gamma;
+        const double r2 = mx * mx + my * my;
+        const double coeff = (xi + sqrt(1.0 + (1.0 - xi * xi) * r2)) / (1.0 + r2);
+        rx = coeff * mx;
+        ry = coeff * my;
+        rz = coeff - xi;
+    }
+    if constexpr (std::is_same<TagT, Tag<RadTan>>::value) {
+        // RadTan::unproject ends its Newton iteration, as the reference does,
+        // once the distortion residual is below 1e-6, so its ray misses the
+        // direction that projects to (u, v) by up to 1e-6 rad: to a two-view
+        // solver that is noise of 5e-4 px on every exact pixel.  Two more
+        // steps of the same (quadratic) iteration square it away twice.
+        const double k1 = c.p[4], k2 = c.p[5], p1 = c.p[6], p2 = c.p[7], k3 = c.p[8];
+        const double tx = (u - c.p[2]) / c.p[0], ty = (v - c.p[3]) / c.p[1];
+        double x = rx / rz, y = ry / rz;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const double r2 = x * x + y * y, r4 = r2 * r2;
+            const double radial = 1.0 + k1 * r2 + k2 * r4 + k3 * r4 * r2;
+            const double ex = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x) - tx;
+            const double ey = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y - ty;
+            // d(xd, yd) / d(x, y) = [[a00, a01], [a01, a11]] (RadTan::project)
+            const double dr = 2.0 * (k1 + 2.0 * k2 * r2 + 3.0 * k3 * r4);
+            const double a00 = radial + dr * x * x + 2.0 * p1 * y + 6.0 * p2 * x;
+            const double a01 = dr * x * y + 2.0 * p1 * x + 2.0 * p2 * y;
+            const double a11 = radial + dr * y * y + 6.0 * p1 * y + 2.0 * p2 * x;
+            const double det = a00 * a11 - a01 * a01;
+            x -= (a11 * ex - a01 * ey) / det;
+            y -= (a00 * ey - a01 * ex) / det;
+        }
+        rx = x;
+        ry = y;
+        rz = 1.0;
+    }
+    const double nr = sqrt(rx * rx + ry * ry + rz * rz);
+    rx /= nr;
+    ry /= nr;
+    rz /= nr;
+    return __builtin_isfinite(rx) && __builtin_isfinite(ry) && __builtin_isfinite(rz);
+}
+
+// (count, score) of pose P over all usable matches, the lanes striding over
+// the matches and their partial sums added by a fixed tree: every lane
+// returns the same pair.  Ends with a barrier after the last read of sh.
+__device__ __forceinline__ void relpose_score(const double (&P)[12], const double* __restrict__ rec,
+                                              size_t stride, long long cnt, double sin2,
+                                              RelPoseShared& sh, int& count, double& score) {
+    const int tid = threadIdx.x;
+    int c = 0;
+    double sum = 0.0;
+    for (long long j = tid; j < cnt; j += kBlock) {
+        const double ax = rec[j];
+        double e;
+        if (__builtin_isfinite(ax) &&
+            essential::inlier(P, ax, rec[stride + j], rec[2 * stride + j], rec[3 * stride + j],
+                              rec[4 * stride + j], rec[5 * stride + j], sin2, e)) {
+            ++c;
+            sum += e;
+        }
+    }
+    sh.cnt[tid] = c;
+    sh.sum[tid] = sum;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            sh.cnt[tid] += sh.cnt[tid + off];
+            sh.sum[tid] += sh.sum[tid + off];
+        }
+        __syncthreads();
+    }
+    count = sh.cnt[0];
+    score = sh.sum[0];
+    __syncthreads();
+}
+
+// One refit round on the model P: the factor of its inliers' rows, the solver
+// on it (cheirality over those inliers), the result Q.  false (workgroup-
+// uniform): no finite result.
+__device__ __forceinline__ bool relpose_refit(const double (&P)[12], const double* __restrict__ rec,
+                                              size_t stride, long long cnt, double sin2,
+                                              RelPoseShared& sh, double (&Q)[12]) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    double T[essential::kTri];
+    essential::clear(T);
+#pragma unroll 1
+    for (long long j = tid; j < cnt; j += kBlock) {
+        const double fa[3] = {rec[j], rec[stride + j], rec[2 * stride + j]};
+        const double fb[3] = {rec[3 * stride + j], rec[4 * stride + j], rec[5 * stride + j]};
+        double e;
+        if (!(__builtin_isfinite(fa[0]) &&
+              essential::inlier(P, fa[0], fa[1], fa[2], fb[0], fb[1], fb[2], sin2, e)))
+            continue;
+        double a[9];
+        essential::row(fa, fb, a);
+        essential::feed(T, a);
+    }
+    // wave merge (fixed butterfly order), then the four waves' factors in order
+#pragma unroll 1
+    for (int off = 32; off > 0; off >>= 1) {
+        double O[essential::kTri];
+#pragma unroll
+        for (int q = 0; q < essential::kTri; ++q) O[q] = __shfl_down(T[q], off, 64);
+        if (lane < off) essential::merge(T, O);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < essential::kTri; ++q) sh.factor[wid][q] = T[q];
+    }
+    if (tid < 4) sh.front[tid] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < essential::kTri; ++q) T[q] = sh.factor[0][q];
+#pragma unroll 1
+    for (int w = 1; w < kBlock / 64; ++w) {
+        double O[essential::kTri];
+#pragma unroll
+        for (int q = 0; q < essential::kTri; ++q) O[q] = sh.factor[w][q];
+        essential::merge(T, O);
+    }
+    // every lane holds the same factor and runs the same solve
+    double E[9], Rp[9], Rm[9], b[3];
+    const bool ok = essential::factor_to_candidates(T, E, Rp, Rm, b);
+    int front[4] = {0, 0, 0, 0};
+    if (ok) {
+        for (long long j = tid; j < cnt; j += kBlock) {
+            const double fa[3] = {rec[j], rec[stride + j], rec[2 * stride + j]};
+            const double fb[3] = {rec[3 * stride + j], rec[4 * stride + j], rec[5 * stride + j]};
+            double e;
+            if (__builtin_isfinite(fa[0]) &&
+                essential::inlier(P, fa[0], fa[1], fa[2], fb[0], fb[1], fb[2], sin2, e))
+                essential::front4(Rp, Rm, b, fa, fb, front);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (front[k]) atomicAdd(&sh.front[k], front[k]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) front[k] = sh.front[k];
+    __syncthreads();  // sh.front and sh.factor may be written again
+    if (!ok) return false;
+    essential::candidate(essential::best_of4(front), Rp, Rm, b, Q);
+    bool fin = true;
+#pragma unroll
+    for (int q = 0; q < 12; ++q) fin = fin && __builtin_isfinite(Q[q]);
+    return fin;
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void relative_pose_pair(const RelPoseArgs& a, size_t pair, long long ob,
+                                                   long long cnt, unsigned usable,
+                                                   const double* __restrict__ rec, size_t stride,
+                                                   RelPoseShared& sh) {
+    const double qnan = __builtin_nan("");
+    const int tid = threadIdx.x;
+    double* dst = reinterpret_cast<double*>(a.poses + pair);
+    if (usable < 8u) {
+        if (tid < 12) dst[tid] = qnan;
+        if (tid == 0) {
+            a.status[pair] = ACM_RELPOSE_TOO_FEW_MATCHES;
+            a.n_inliers[pair] = 0;
+        }
+        if (a.mask)
+            for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
+        return;
+    }
+    // the lane's best: count (-1: no model), score, hypothesis, pose
+    int bc = -1, bh = 0;
+    double bsum = 0.0, bp[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) bp[k] = qnan;
+#pragma unroll 1
+    for (int h = tid; h < a.H; h += kBlock) {
+        RelPoseSample s;
+        int got = 0;
+#pragma unroll 1
+        for (int d = 0; d < 16 && got < 8; ++d) {
+            const unsigned long long ctr = 16ull * (unsigned long long)h + (unsigned long long)d + 1ull;
+            const unsigned long long r = pose_est_mix(a.seed + ctr * 0x9E3779B97F4A7C15ull);
+            const long long j = (long long)__umul64hi(r, (unsigned long long)cnt);
+            if (!__builtin_isfinite(rec[j]) || s.has(j)) continue;
+            s.set(got, j);
+            ++got;
+        }
+        if (got < 8) continue;
+        double P[12], E[9];
+        essential::solve_rows(
+            8,
+            [=](long long i, double(&fa)[3], double(&fb)[3]) {
+                const long long j = s.get((int)i);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    fa[k] = rec[k * stride + j];
+                    fb[k] = rec[(3 + k) * stride + j];
+                }
+                return true;
+            },
+            P, E);
+        if (!__builtin_isfinite(P[0])) continue;
+        int c = 0;
+        double sum = 0.0;
+        for (long long j = 0; j < cnt; ++j) {
+            const double ax = rec[j];
+            if (!__builtin_isfinite(ax)) continue;
+            double e;
+            if (essential::inlier(P, ax, rec[stride + j], rec[2 * stride + j], rec[3 * stride + j],
+                                  rec[4 * stride + j], rec[5 * stride + j], a.sin2, e)) {
+                ++c;
+                sum += e;
+            }
+        }
+        // h only grows in a lane: a tie keeps the earlier
+        if (c > bc || (c == bc && sum < bsum)) {
+            bc = c;
+            bsum = sum;
+            bh = h;
+#pragma unroll
+            for (int q = 0; q < 12; ++q) bp[q] = P[q];
+        }
+    }
+    sh.cnt[tid] = bc;
+    sh.sum[tid] = bsum;
+    sh.h[tid] = bh;
+    sh.lane[tid] = tid;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            const int o = tid + off;
+            const int c0 = sh.cnt[tid], c1 = sh.cnt[o];
+            const double u0 = sh.sum[tid], u1 = sh.sum[o];
+            const int h0 = sh.h[tid], h1 = sh.h[o];
+            const bool take = c1 > c0 || (c1 == c0 && c1 >= 0 && (u1 < u0 || (u1 == u0 && h1 < h0)));
+            if (take) {
+                sh.cnt[tid] = c1;
+                sh.sum[tid] = u1;
+                sh.h[tid] = h1;
+                sh.lane[tid] = sh.lane[o];
+            }
+        }
+        __syncthreads();
+    }
+    int best = sh.cnt[0];
+    double best_sum = sh.sum[0];
+    const int winner = sh.lane[0];
+    if (best < a.min_inliers) {  // also no model at all: best = -1
+        if (tid < 12) dst[tid] = qnan;
+        if (tid == 0) {
+            a.status[pair] = ACM_RELPOSE_NO_MODEL;
+            a.n_inliers[pair] = best < 0 ? 0u : (uint32_t)best;
+        }
+        if (a.mask)
+            for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
+        return;
+    }
+    if (tid == winner) {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) sh.pose[q] = bp[q];
+    }
+    __syncthreads();
+    double P[12];
+#pragma unroll
+    for (int q = 0; q < 12; ++q) P[q] = sh.pose[q];
+    __syncthreads();  // sh.cnt and sh.sum are written again below
+    // the refit: every condition below is the same in all lanes
+#pragma unroll 1
+    for (int round = 0; round < a.refit_rounds; ++round) {
+        double Q[12];
+        if (!relpose_refit(P, rec, stride, cnt, a.sin2, sh, Q)) break;
+        int c;
+        double sum;
+        relpose_score(Q, rec, stride, cnt, a.sin2, sh, c, sum);
+        if (!(c > best || (c == best && sum < best_sum))) break;
+        best = c;
+        best_sum = sum;
+#pragma unroll
+        for (int q = 0; q < 12; ++q) P[q] = Q[q];
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 0; q < 12; ++q) dst[q] = P[q];
+        a.status[pair] = ACM_RELPOSE_OK;
+        a.n_inliers[pair] = (uint32_t)best;
+    }
+    if (a.mask) {
+        for (long long j = tid; j < cnt; j += kBlock) {
+            const double ax = rec[j];
+            double e;
+            const bool in = __builtin_isfinite(ax) &&
+                            essential::inlier(P, ax, rec[stride + j], rec[2 * stride + j],
+                                              rec[3 * stride + j], rec[4 * stride + j],
+                                              rec[5 * stride + j], a.sin2, e);
+            a.mask[ob + j] = in ? 1 : 0;
+        }
+    }
+}
+
+template <class TagT>
+__global__ __launch_bounds__(kBlock) void k_relative_pose(CamArg cam, RelPoseArgs a) {
+    __shared__ double s_rec[6 * kRelPoseStage];  // planes fa.x, fa.y, fa.z, fb.x, fb.y, fb.z
+    __shared__ RelPoseShared sh;
+    const Cam<double> c = make_cam<double>(cam);
+    const size_t pair = blockIdx.x;
+    // the pair's matches, clamped into [0, n_matches] (k_pose_estimate)
+    const long long nm = (long long)a.n_matches;
+    long long ob = a.offs[pair], oe = a.offs[pair + 1];
+    ob = ob < 0 ? 0 : (ob > nm ? nm : ob);
+    oe = oe < ob ? ob : (oe > nm ? nm : oe);
+    const long long cnt = oe - ob;
+    const bool staged = cnt <= (long long)kRelPoseStage;  // workgroup-uniform
+    const double qnan = __builtin_nan("");
+    if (threadIdx.x == 0) sh.usable = 0u;
+    __syncthreads();
+    // the records: j < cnt <= n_matches - ob, so a workspace plane is never overrun
+    double* wrec = a.ws + ob;
+    const size_t wstride = a.n_matches;
+    unsigned mine = 0;
+    for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+        double f[6];
+        const bool ok =
+            relpose_bearing<TagT>(c, a.uv_a[2 * (ob + j)], a.uv_a[2 * (ob + j) + 1], f[0], f[1], f[2]) &&
+            relpose_bearing<TagT>(c, a.uv_b[2 * (ob + j)], a.uv_b[2 * (ob + j) + 1], f[3], f[4], f[5]);
+        if (ok) ++mine;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const double v = ok ? f[q] : qnan;
+            if (staged) s_rec[q * kRelPoseStage + j] = v;
+            else wrec[q * wstride + j] = v;
+        }
+    }
+    if (mine) atomicAdd(&sh.usable, mine);
+    __threadfence_block();
+    __syncthreads();
+    const unsigned usable = sh.usable;
+    if (threadIdx.x == 0 && a.n_usable) a.n_usable[pair] = usable;
+    if (staged)
+        relative_pose_pair<true>(a, pair, ob, cnt, usable, s_rec, (size_t)kRelPoseStage, sh);
+    else
+        relative_pose_pair<false>(a, pair, ob, cnt, usable, wrec, wstride, sh);
 }
 
 // ------------------------------------------------------------ calibration
@@ -7061,6 +7495,84 @@ ACM_API int acm_pose_estimate_batch(const acm_camera* cam, size_t n_views, acm_p
         hipLaunchKernelGGL(k_pose_estimate<TagT>, dim3((unsigned)n_views), dim3(kBlock), 0, s,
                            prep(*cam, false, true), a);
         return check_launch("acm_pose_estimate_batch");
+    });
+}
+
+ACM_API int acm_relative_pose_8pt(size_t n, const double* bearings_a, const double* bearings_b,
+                                  acm_pose* poses, double* essential, uint8_t* n_front,
+                                  void* stream) {
+    if (n == 0) return ACM_SUCCESS;
+    if (!bearings_a || !bearings_b || !poses || !n_front)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (n > (size_t)0x7fffffff * kBlock)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many problems for one launch");
+    const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_relative_pose_8pt, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, n,
+                       bearings_a, bearings_b, poses, essential, n_front);
+    return check_launch("acm_relative_pose_8pt");
+}
+
+ACM_API void acm_relative_pose_batch_default_config(acm_relative_pose_config* cfg) {
+    if (!cfg) return;
+    cfg->n_hypotheses = 512;
+    cfg->flags = 0;
+    cfg->seed = 1;
+    cfg->inlier_angle = 5e-3;
+    cfg->min_inliers = 8;
+    cfg->refit_rounds = 3;
+}
+
+// 64 reserved bytes, then the records of the pairs too long for LDS: six
+// planes of n_matches doubles (a pair uses its own range of each plane)
+ACM_API size_t acm_relative_pose_batch_workspace_size(size_t, size_t n_matches) {
+    return 64 + 48 * n_matches;
+}
+
+ACM_API int acm_relative_pose_batch(const acm_camera* cam, size_t n_pairs, acm_pose* poses,
+                                    const int64_t* pair_offsets, size_t n_matches,
+                                    const double* uv_a, const double* uv_b,
+                                    const acm_relative_pose_config* cfg, uint8_t* status,
+                                    uint32_t* n_inliers, uint8_t* inlier_mask, uint32_t* n_usable,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
+    if (cfg->n_hypotheses < 1 || cfg->n_hypotheses > 65536 || cfg->flags != 0 ||
+        !(cfg->inlier_angle > 0.0 && cfg->inlier_angle < kPi / 2.0) || cfg->min_inliers < 8 ||
+        cfg->refit_rounds < 0 || cfg->refit_rounds > 8)
+        return fail(ACM_ERR_INVALID_ARGUMENT,
+                    "n_hypotheses outside 1 .. 65536, nonzero flags, inlier_angle outside (0, pi/2), "
+                    "min_inliers < 8 or refit_rounds outside 0 .. 8");
+    if (n_pairs == 0) return ACM_SUCCESS;
+    if (!poses || !pair_offsets || !status || !n_inliers || (n_matches && (!uv_a || !uv_b)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace || workspace_bytes < acm_relative_pose_batch_workspace_size(n_pairs, n_matches))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "relative pose workspace too small");
+    if (n_pairs > (size_t)0x7fffffff)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many pairs for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_model(cam->model, [&](auto tag) -> int {
+        using TagT = decltype(tag);
+        RelPoseArgs a;
+        a.n_matches = n_matches;
+        a.poses = poses;
+        a.offs = pair_offsets;
+        a.uv_a = uv_a;
+        a.uv_b = uv_b;
+        a.status = status;
+        a.n_inliers = n_inliers;
+        a.mask = inlier_mask;
+        a.n_usable = n_usable;
+        a.ws = reinterpret_cast<double*>(static_cast<char*>(workspace) + 64);
+        a.H = cfg->n_hypotheses;
+        a.min_inliers = cfg->min_inliers;
+        a.refit_rounds = cfg->refit_rounds;
+        a.seed = cfg->seed;
+        const double si = std::sin(cfg->inlier_angle);
+        a.sin2 = si * si;
+        hipLaunchKernelGGL(k_relative_pose<TagT>, dim3((unsigned)n_pairs), dim3(kBlock), 0, s,
+                           prep(*cam, false, true), a);
+        return check_launch("acm_relative_pose_batch");
     });
 }
 

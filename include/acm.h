@@ -802,6 +802,161 @@ ACM_API int acm_pose_estimate_batch(const acm_camera *cam, size_t n_views, acm_p
                                     uint32_t *n_usable, void *workspace,
                                     size_t workspace_bytes, void *stream);
 
+/* Two-view relative pose: the 8-point solver and RANSAC over it.  Everything
+ * above needs a pose or known 3-D points from outside; these two calls produce
+ * the pose of camera B relative to camera A from 2-D / 2-D matches alone, and
+ * the set of matches that agree with it, so acm_triangulate can start from two
+ * images of an unknown scene.  Convention for both: p_b = R p_a + t with
+ * |t| = 1 (the scale is unobservable), E = [t]x R and f_b^T E f_a = 0 for the
+ * bearings f_a, f_b of a match; the output is an acm_pose.  The solver works
+ * on bearing vectors, not on normalised pixels, because most of the models are
+ * omnidirectional.
+ *
+ * acm_relative_pose_8pt: n independent problems of eight matches, one lane
+ * each.  bearings_a, bearings_b: 24 n f64, problem i holds its eight bearings
+ * in image A and in image B (any length; the call normalises them).  poses: n
+ * acm_pose; essential (nullable): 9 n f64, E row-major with unit Frobenius
+ * norm, signed as [t]x R; n_front: n bytes, the number of the eight matches in
+ * front of both cameras of the returned pose.
+ *
+ * The route, f64 throughout, works for any row count >= 8 (the refit below
+ * reuses it).  Match i gives the row a = f_b (x) f_a (nine entries, E
+ * row-major, so a . vec(E) = f_b^T E f_a).  The rows are streamed through
+ * Givens rotations into a 9 x 9 upper-triangular factor R9 -- no pivoting, no
+ * normal equations (A^T A squares the conditioning: its Cholesky route lost
+ * two digits in the median and had a tail of gross errors) -- and a diagonal
+ * entry with |r_kk| < 2^-60 max |R9| is replaced by that value with its sign
+ * (with eight rows the last entry is exactly 0).  The null vector is the
+ * smallest right singular vector of R9 by three rounds of inverse iteration
+ * on R9^T R9 (solve R9^T z = x, normalise, solve R9 y = z, normalise) from
+ * x0 ~ (1, 2, ..., 9); no component is fixed to 1, so motions with zeros in E
+ * (forward: a zero row; sideways: a zero diagonal) work.  E is decomposed in
+ * closed form, without an SVD (Horn 1990): B = tr(E E^T) / 2 I - E E^T = b b^T
+ * gives b as B's column of the largest diagonal entry over the root of that
+ * entry; with C the matrix of the rows e2 x e3, e3 x e1, e1 x e2 of E's rows,
+ * R+- = (C -+ [b]x E) / (b . b), each made a rotation by Gram-Schmidt on rows
+ * 0 and 1 and the cross product as row 2.  The four candidates are, in order,
+ * (R+, b^), (R+, -b^), (R-, -b^), (R-, b^).  A match is in front of both
+ * cameras iff, with g = R f_a and c = g . f_b, c (f_b . t) - g . t > 0 and
+ * (f_b . t) - c (g . t) > 0 (no division); the candidate with the most rows in
+ * front wins, the first of equals.
+ *
+ * A non-finite input, a bearing without direction or a non-finite result: the
+ * pose and the essential matrix all NaN, n_front = 0.  Degenerate inputs --
+ * rows whose null space has dimension >= 2: repeated matches, all points on
+ * one plane, pure rotation -- return some member of that null space with no
+ * guarantee; the RANSAC below discards them by their score.  n = 0 is valid.
+ * NULL buffers (essential excepted) with n > 0: ACM_ERR_INVALID_ARGUMENT.  No
+ * workspace, stream-ordered, reentrant.
+ *
+ * acm_relative_pose_batch: RANSAC over that solver, one 256-lane workgroup per
+ * view pair, all pairs in one launch.  Matches are CSR by pair: pair k owns
+ * the matches pair_offsets[k] .. pair_offsets[k + 1] - 1 (offsets clamped
+ * into [0, n_matches] as acm_pose_estimate_batch clamps its own), uv_a and
+ * uv_b (2 n_matches f64 each) their pixels in image A and in image B.  One
+ * camera serves both images of every pair.
+ *
+ * A match is usable iff both pixels are finite and both unprojections
+ * (acm_unproject's default numerics) are Ok with a finite direction; its
+ * bearings are those rays, normalised, with two exceptions in which that
+ * unprojection still decides Ok: for UCM the bearing is the projection's
+ * inverse, as acm_pose_estimate_batch documents; for RadTan, whose
+ * unprojection ends its Newton iteration once the distortion residual is
+ * below 1e-6 and so misses the direction that projects to the pixel by up to
+ * 1e-6 rad (an exact pair of 8 matches finds no model with such rays at a
+ * 1e-6 rad threshold), the bearing is that ray after two more steps of the
+ * same iteration.  n_usable (nullable) receives the count
+ * per pair.  The pair's records (f_a, f_b; 48 B) are built once: in LDS for a
+ * pair of at most ACM_RELPOSE_STAGE_MATCHES matches, in the workspace
+ * otherwise (the same arithmetic in the same order), so an iterative
+ * unprojection (KB, RadTan) runs twice per match, never per hypothesis.
+ *
+ * Hypothesis h = 0 .. n_hypotheses - 1 (lanes stride over h) draws local
+ * indices with acm_pose_estimate_batch's splitmix64 and ctr = 16 h + d + 1
+ * for the draws d = 0 .. 15.  The first eight draws that are usable and
+ * pairwise distinct form the sample; if sixteen draws do not yield eight the
+ * hypothesis is void.  The sample goes through the solver above (cheirality
+ * over its eight matches) and the pose is scored over all usable matches of
+ * the pair in order: with g = R f_a, n = t x g and d = f_b . n, a match is an
+ * inlier iff n . n > 0, d^2 <= sin^2(inlier_angle) (n . n) -- f_b lies within
+ * inlier_angle of the epipolar plane -- and both cheirality expressions above
+ * are positive.  A match without parallax carries no depth sign and is not
+ * counted.  The key of a hypothesis is (inlier count descending, sum over the
+ * inliers of d^2 / (n . n) ascending, h ascending), a total order, so the
+ * winner does not depend on the order of the reduction.
+ *
+ * Refit.  A minimal sample of noisy matches is a weak estimate, so when the
+ * winner has at least min_inliers inliers, up to refit_rounds times the
+ * workgroup streams the rows of the current model's inliers into R9 -- lane l
+ * takes the matches l, l + 256, ... in order, the 64 factors of a wave are
+ * merged by a fixed butterfly (one factor's rows are fed into the other),
+ * then the four waves' in order, so the result depends on nothing but the
+ * match list -- runs the solver on that factor (cheirality over those
+ * inliers) and scores the result over all usable matches.  It replaces the
+ * current model iff its (count descending, score ascending) is strictly
+ * better; otherwise, or when the solve fails, the loop ends.
+ *
+ * Outputs per pair: the pose, status (acm_relpose_status, required),
+ * n_inliers (required) and, when non-NULL, inlier_mask (one byte per match, 1
+ * for the final model's inliers, 0 for every other entry of the pair's
+ * clamped range, unusable matches included).  Fewer than 8 usable matches:
+ * ACM_RELPOSE_TOO_FEW_MATCHES, the pose all NaN, n_inliers = 0, the mask 0.
+ * No hypothesis with a finite model, or a best count below min_inliers (the
+ * refit is not tried then): ACM_RELPOSE_NO_MODEL, the pose NaN, n_inliers =
+ * the best count (0 without a model), the mask 0.  Pairs whose clamped ranges
+ * overlap (which valid offsets never do) write the same mask bytes and
+ * workspace records from several workgroups.
+ *
+ * A pair's outputs depend only on its own match list in order, the camera and
+ * the config -- not on n_pairs, its index or the other pairs -- and repeated
+ * calls return the same bits.
+ *
+ * Errors: acm_pose_estimate_batch's list (workspace: device, 8-byte aligned,
+ * acm_relative_pose_batch_workspace_size bytes), and ACM_ERR_INVALID_ARGUMENT
+ * for n_hypotheses outside 1 .. 65536, nonzero flags, inlier_angle outside
+ * (0, pi/2), min_inliers < 8 or refit_rounds outside 0 .. 8.  n_pairs = 0 is
+ * valid and touches nothing.  Stream-ordered, no allocation, no host
+ * synchronisation, reentrant (two calls in flight need two workspaces).
+ *
+ * Out of scope: a 5-point minimal solver (it survives planar scenes and needs
+ * 5 instead of 8 clean matches per sample, but its 10 x 20 elimination and
+ * degree-10 root finding do not fit a lane's registers); detection of pure
+ * rotation and planar scenes (acm_triangulate's ACM_TRI_DEGENERATE reports the
+ * missing parallax downstream); a non-linear refinement of E; two different
+ * cameras per pair; spreading one pair's hypotheses over several workgroups. */
+ACM_API int acm_relative_pose_8pt(size_t n, const double *bearings_a, const double *bearings_b,
+                                  acm_pose *poses, double *essential, uint8_t *n_front,
+                                  void *stream);
+
+typedef enum acm_relpose_status {
+    ACM_RELPOSE_OK = 0,
+    ACM_RELPOSE_TOO_FEW_MATCHES = 1, /* fewer than 8 usable matches */
+    ACM_RELPOSE_NO_MODEL = 2         /* no finite model, or fewer than min_inliers inliers */
+} acm_relpose_status;
+
+/* matches of one pair whose records stay in LDS (48 B each); a longer pair
+ * keeps them in the workspace */
+#define ACM_RELPOSE_STAGE_MATCHES 1024
+
+typedef struct acm_relative_pose_config {
+    int32_t n_hypotheses;   /* default 512; 1 .. 65536 */
+    int32_t flags;          /* must be 0 */
+    uint64_t seed;          /* default 1 */
+    double inlier_angle;    /* radians, in (0, pi/2); default 5e-3 */
+    int32_t min_inliers;    /* default 8; >= 8 */
+    int32_t refit_rounds;   /* default 3; 0 .. 8 */
+} acm_relative_pose_config;
+
+ACM_API void acm_relative_pose_batch_default_config(acm_relative_pose_config *cfg);
+ACM_API size_t acm_relative_pose_batch_workspace_size(size_t n_pairs, size_t n_matches);
+ACM_API int acm_relative_pose_batch(const acm_camera *cam, size_t n_pairs, acm_pose *poses,
+                                    const int64_t *pair_offsets, size_t n_matches,
+                                    const double *uv_a, const double *uv_b,
+                                    const acm_relative_pose_config *cfg, uint8_t *status,
+                                    uint32_t *n_inliers, uint8_t *inlier_mask,
+                                    uint32_t *n_usable, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+
 /* Multi-view calibration: the intrinsics and every view's pose in one
  * Levenberg-Marquardt.  K views of known world points, rough poses (device,
  * in/out) and rough intrinsics (cam, host, in/out); the unknowns are the P
