@@ -31,6 +31,7 @@
 
 #include "acm.h"
 #include "camera_models.hpp"
+#include "batch_solvers.hpp"
 #include "lm_core.hpp"
 #include "lm_doorbell.hpp"
 #include "p3p.hpp"
@@ -1468,7 +1469,7 @@ __global__ void k_ne_publish(unsigned long long* __restrict__ flag, unsigned lon
 // point whose projection is not Ok or whose observation is NaN is skipped.
 // 40 B per point read (two points' loads in flight behind the current one's
 // math), nothing per point written.
-constexpr int kPoseK = 29;
+constexpr int kPoseK = 29;  // normal_eq_accumulate<6>'s sums
 constexpr int kPoseAhead = 2;  // points in flight per lane
 
 template <class TagT, int LAYOUT>
@@ -1494,28 +1495,18 @@ __global__ __launch_bounds__(kBlock) void k_pose_normal_eq(CamArg cam, acm_pose 
         load_point<LAYOUT, true>(pts, n, ic, xs[q], ys[q], zs[q]);
         os[q] = ld2<true>(obs + 2 * ic);
     };
+    const double P12[12] = {pose.r[0], pose.r[1], pose.r[2], pose.r[3], pose.r[4], pose.r[5],
+                            pose.r[6], pose.r[7], pose.r[8], pose.t[0], pose.t[1], pose.t[2]};
     auto accumulate = [&](double X, double Y, double Z, double2 o) {
-        const double px = pose.r[0] * X + pose.r[1] * Y + pose.r[2] * Z + pose.t[0];
-        const double py = pose.r[3] * X + pose.r[4] * Y + pose.r[5] * Z + pose.t[1];
-        const double pz = pose.r[6] * X + pose.r[7] * Y + pose.r[8] * Z + pose.t[2];
+        double px, py, pz;
+        transform_point(P12, X, Y, Z, px, py, pz);
         double u, v, ju[3], jv[3];
         const uint8_t st = M::template project<false, true, false, true>(c, px, py, pz, u, v, ju, jv);
         if (st == ST_OK && o.x == o.x && o.y == o.y) {
             const double r0 = u - o.x, r1 = v - o.y;
-            const double a[6] = {ju[0], ju[1], ju[2], py * ju[2] - pz * ju[1],
-                                 pz * ju[0] - px * ju[2], px * ju[1] - py * ju[0]};
-            const double b[6] = {jv[0], jv[1], jv[2], py * jv[2] - pz * jv[1],
-                                 pz * jv[0] - px * jv[2], px * jv[1] - py * jv[0]};
-            int k = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-#pragma unroll
-                for (int q = r; q < 6; ++q, ++k) acc[k] = fma(a[r], a[q], fma(b[r], b[q], acc[k]));
-            }
-#pragma unroll
-            for (int r = 0; r < 6; ++r) acc[21 + r] = fma(a[r], r0, fma(b[r], r1, acc[21 + r]));
-            acc[27] = fma(r0, r0, fma(r1, r1, acc[27]));
-            acc[28] += 1.0;
+            double a[6], b[6];
+            pose_rows(ju, jv, px, py, pz, a, b);
+            normal_eq_accumulate<6>(acc, a, b, r0, r1);
         }
     };
     if (n) {
@@ -1600,29 +1591,6 @@ struct TriArgs {
     double ctol, ptol, gtol, mu0, sin2;
 };
 
-// A x = b for the symmetric A = [00 01 02 11 12 22] by Cholesky, in
-// lm::cholesky_solve's operation order; false when A is not positive definite
-__device__ __forceinline__ bool tri_chol3(const double* A, const double* b, double* x) {
-    if (!(A[0] > 0.0)) return false;
-    const double l00 = sqrt(A[0]);
-    const double l10 = A[1] / l00;
-    const double s11 = A[3] - l10 * l10;
-    if (!(s11 > 0.0)) return false;
-    const double l11 = sqrt(s11);
-    const double l20 = A[2] / l00;
-    const double l21 = (A[4] - l20 * l10) / l11;
-    const double s22 = A[5] - l20 * l20 - l21 * l21;
-    if (!(s22 > 0.0)) return false;
-    const double l22 = sqrt(s22);
-    const double y0 = b[0] / l00;
-    const double y1 = (b[1] - l10 * y0) / l11;
-    const double y2 = (b[2] - l20 * y0 - l21 * y1) / l22;
-    x[2] = y2 / l22;
-    x[1] = (y1 - l21 * x[2]) / l11;
-    x[0] = (y0 - l10 * x[1] - l20 * x[2]) / l00;
-    return true;
-}
-
 template <class TagT>
 __global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
     using M = typename TagT::template type<double>;
@@ -1642,15 +1610,11 @@ __global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
     const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
     if (i - (size_t)lane >= a.n_points) return;  // wave-uniform
     const bool live = i < a.n_points;
-    // the lane's track, clamped into [0, n_obs]: no offset reads out of bounds
+    // the lane's track [tb, te) inside [0, n_obs]
     const long long nobs = (long long)a.n_obs;
-    long long tb = 0, te = 0;
-    if (live) {
-        tb = a.offs[i];
-        te = a.offs[i + 1];
-        tb = tb < 0 ? 0 : (tb > nobs ? nobs : tb);
-        te = te < tb ? tb : (te > nobs ? nobs : te);
-    }
+    long long tb = 0, tn = 0;
+    if (live) clamped_range(a.offs, i, a.n_obs, tb, tn);
+    const long long te = tb + tn;
     // the wave's run [rb, re)
     long long rb = live ? tb : nobs, re = live ? te : 0;
 #pragma unroll
@@ -1740,7 +1704,7 @@ __global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
         x[2] = (k02 * b0 + k12 * b1 + k22 * b2) / det;
     }
 
-    // LM (lm_core.hpp consume / advance, P = 3): x the accepted point with
+    // LM (batch_solvers.hpp's pieces, P = 3): x the accepted point with
     // its A = J^T J (upper triangle), g = J^T r, F, nv; xn the point under
     // evaluation, h = xn - x.  term: 0 running, 1 a tolerance, 2 failed.
     double xn[3] = {x[0], x[1], x[2]}, h[3] = {0.0, 0.0, 0.0};
@@ -1759,9 +1723,8 @@ __global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
             if (!(__builtin_isfinite(u) && __builtin_isfinite(v))) continue;
             if (vi < 0 || (size_t)vi >= a.n_views) continue;
             const double* P = pp + 12 * (size_t)vi;
-            const double px = P[0] * xn[0] + P[1] * xn[1] + P[2] * xn[2] + P[9];
-            const double py = P[3] * xn[0] + P[4] * xn[1] + P[5] * xn[2] + P[10];
-            const double pz = P[6] * xn[0] + P[7] * xn[1] + P[8] * xn[2] + P[11];
+            double px, py, pz;
+            transform_point(P, xn[0], xn[1], xn[2], px, py, pz);
             double pu, pv, ju[3], jv[3];
             if (M::template project<false, true, false, true>(c, px, py, pz, pu, pv, ju, jv) != ST_OK)
                 continue;
@@ -1795,24 +1758,11 @@ __global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
             if (a.max_it == 0) term = 1;
             else if (!__builtin_isfinite(Fn)) term = 2;
         } else {
-            // predicted reduction L(0) - L(h) = -(g.h + 0.5 h.A.h)
-            const double t0 = A[0] * h[0] + A[1] * h[1] + A[2] * h[2];
-            const double t1 = A[1] * h[0] + A[3] * h[1] + A[4] * h[2];
-            const double t2 = A[2] * h[0] + A[4] * h[1] + A[5] * h[2];
-            const double gh = g[0] * h[0] + g[1] * h[1] + g[2] * h[2];
-            const double hAh = h[0] * t0 + h[1] * t1 + h[2] * t2;
-            const double pred = -(gh + 0.5 * hAh);
-            const double rho = (__builtin_isfinite(Fn) && pred > 0.0 && nvn >= nv) ? (F - Fn) / pred : -1.0;
-            if (rho > 0.0) {
-                accept = true;
-                const double t = 2.0 * rho - 1.0;
-                mu *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-                nu = 2.0;
-            } else {
-                mu *= nu;
-                nu *= 2.0;
-                if (!__builtin_isfinite(mu) || mu > 1e32) term = 2;
-            }
+            // a trial that lost valid observations is rejected whatever its cost
+            const double pred = lm::predicted_reduction<3>(A, g, h);
+            const int gain = lm::gain_update(lm::gain_ratio(F, Fn, pred, nvn >= nv), mu, nu);
+            accept = gain == lm::GAIN_ACCEPT;
+            if (gain == lm::GAIN_FAILED) term = 2;
         }
         if (accept) {
             const double dF = F - Fn, Fold = F;
@@ -1825,45 +1775,13 @@ __global__ __launch_bounds__(kBlock) void k_triangulate(CamArg cam, TriArgs a) {
             for (int k = 0; k < 3; ++k) g[k] = gn[k];
             F = Fn;
             nv = nvn;
-            if (term == 0) {
-                if (fmax(fabs(g[0]), fmax(fabs(g[1]), fabs(g[2]))) <= a.gtol) term = 1;
-                else if (trial && dF <= a.ctol * Fold) term = 1;
-            }
+            if (term == 0 && lm::accepted_terminates<3>(g, a.gtol, trial, dF, Fold, a.ctol)) term = 1;
         }
         // advance to the next point to evaluate, or end
-        bool need = false;
-        while (term == 0 && it < a.max_it) {
-            ++it;
-            double Ad[6] = {A[0], A[1], A[2], A[3], A[4], A[5]};
-            const double floor_d = 1e-12 * fmax(dmax, 1.0);
-            Ad[0] += mu * fmax(A[0], floor_d);
-            Ad[3] += mu * fmax(A[3], floor_d);
-            Ad[5] += mu * fmax(A[5], floor_d);
-            const double mg[3] = {-g[0], -g[1], -g[2]};
-            double hs[3];
-            if (!tri_chol3(Ad, mg, hs)) {
-                mu *= nu;
-                nu *= 2.0;
-                continue;
-            }
-            double hn = 0.0, xnorm = 0.0;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                xn[k] = x[k] + hs[k];
-                h[k] = xn[k] - x[k];
-                hn += h[k] * h[k];
-                xnorm += x[k] * x[k];
-            }
-            hn = sqrt(hn);
-            xnorm = sqrt(xnorm);
-            if (hn <= a.ptol * (xnorm + a.ptol)) {
-                term = 1;
-                break;
-            }
-            need = true;
-            break;
-        }
-        if (!need) break;
+        if (term != 0) break;
+        const int step = lm::next_step<3>(A, g, x, mu, nu, dmax, a.ptol, it, a.max_it, xn, h);
+        if (step == lm::STEP_CONVERGED) term = 1;
+        if (step != lm::STEP_EVALUATE) break;
     }
     finish(term == 1 ? ACM_TRI_OK : ACM_TRI_NOT_CONVERGED, x[0], x[1], x[2], F, nv, A);
 }
@@ -1938,48 +1856,77 @@ __device__ __forceinline__ void block_sum_lds(const double (&acc)[K], double (&s
     __syncthreads();
 }
 
-// index of (r, q), r <= q, in the row-by-row upper triangle of a 6 x 6
-__host__ __device__ constexpr int pose_ut(int r, int q) {
-    return r <= q ? r * 6 - r * (r - 1) / 2 + (q - r) : q * 6 - q * (q - 1) / 2 + (r - q);
+// A view's observations as k_pose_batch and k_calib_eval read them: the
+// range [ob, ob + cnt) of (point index, pixel), the world points gathered by
+// index.  Staged once in LDS (x, y, z, u, v planes) when the view has at most
+// kPoseStageObs of them; a longer view gathers from global memory at every
+// evaluation (same arithmetic, same order, same bits).
+struct ViewObs {
+    size_t n_points;
+    const double* X;
+    const int32_t* pt;
+    const double* uv;
+    long long ob, cnt;
+    bool staged;  // workgroup-uniform
+};
+
+// observation j of the view from global memory: the pixel and the gathered
+// world point, the point NaN when its index is out of range (never
+// dereferenced) or it is not finite -- the caller skips on X
+__device__ __forceinline__ void gather_view_observation(const ViewObs& o, long long j, double& X,
+                                                        double& Y, double& Z, double& u, double& v) {
+    const double qnan = __builtin_nan("");
+    const int32_t pi = o.pt[o.ob + j];
+    u = o.uv[2 * (o.ob + j)];
+    v = o.uv[2 * (o.ob + j) + 1];
+    X = Y = Z = qnan;
+    if (pi >= 0 && (size_t)pi < o.n_points) {
+        X = o.X[3 * (size_t)pi];
+        Y = o.X[3 * (size_t)pi + 1];
+        Z = o.X[3 * (size_t)pi + 2];
+    }
+    if (!(__builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z))) X = Y = Z = qnan;
 }
 
-// A x = b for the symmetric 6 x 6 A (upper triangle, 21) by Cholesky, in
-// lm::cholesky_solve's operation order, every index a compile-time constant;
-// false when A is not positive definite
-__device__ __forceinline__ bool pose_chol6(const double (&A)[21], const double (&b)[6],
-                                           double (&x)[6]) {
-    double L[21];  // lower triangle, (i, j) at pose_ut(j, i)
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-#pragma unroll
-        for (int j = 0; j <= i; ++j) {
-            double s = A[pose_ut(j, i)];
-#pragma unroll
-            for (int q = 0; q < j; ++q) s -= L[pose_ut(q, i)] * L[pose_ut(q, j)];
-            if (i == j) {
-                if (!(s > 0.0)) return false;
-                L[pose_ut(i, i)] = sqrt(s);
-            } else {
-                L[pose_ut(j, i)] = s / L[pose_ut(j, j)];
-            }
+// the whole workgroup: clamp the view's range and stage it if it fits
+__device__ __forceinline__ ViewObs stage_view_observations(size_t n_points, const double* X,
+                                                           const int64_t* offs, size_t view,
+                                                           size_t n_obs, const int32_t* pt,
+                                                           const double* uv,
+                                                           double (&s_obs)[5][kPoseStageObs]) {
+    ViewObs o{n_points, X, pt, uv, 0, 0, false};
+    clamped_range(offs, view, n_obs, o.ob, o.cnt);
+    o.staged = o.cnt <= (long long)kPoseStageObs;
+    if (o.staged) {
+        for (long long j = threadIdx.x; j < o.cnt; j += kBlock) {
+            double Xj, Yj, Zj, u, v;
+            gather_view_observation(o, j, Xj, Yj, Zj, u, v);
+            s_obs[0][j] = Xj;
+            s_obs[1][j] = Yj;
+            s_obs[2][j] = Zj;
+            s_obs[3][j] = u;
+            s_obs[4][j] = v;
         }
+        __syncthreads();
     }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double s = b[i];
-#pragma unroll
-        for (int q = 0; q < i; ++q) s -= L[pose_ut(q, i)] * y[q];
-        y[i] = s / L[pose_ut(i, i)];
+    return o;
+}
+
+// false: the observation is unusable (a pixel or a point that is not finite)
+__device__ __forceinline__ bool load_view_observation(const ViewObs& o,
+                                                      const double (&s_obs)[5][kPoseStageObs],
+                                                      long long j, double& X, double& Y, double& Z,
+                                                      double& u, double& v) {
+    if (o.staged) {
+        X = s_obs[0][j];
+        Y = s_obs[1][j];
+        Z = s_obs[2][j];
+        u = s_obs[3][j];
+        v = s_obs[4][j];
+    } else {
+        gather_view_observation(o, j, X, Y, Z, u, v);
     }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double s = y[i];
-#pragma unroll
-        for (int q = i + 1; q < 6; ++q) s -= L[pose_ut(i, q)] * x[q];
-        x[i] = s / L[pose_ut(i, i)];
-    }
-    return true;
+    return __builtin_isfinite(u) && __builtin_isfinite(v) && __builtin_isfinite(X);
 }
 
 // acm_pose_retract's formulas in double: out = (Exp(phi) R, Exp(phi) t + rho)
@@ -2025,42 +1972,9 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
     __shared__ double s_st[2][kStSize];
     const Cam<double> c = make_cam<double>(cam);
     const size_t view = blockIdx.x;
-    // the view's observations, clamped into [0, n_obs]: no offset reads out of bounds
-    const long long nobs = (long long)a.n_obs;
-    long long ob = a.offs[view], oe = a.offs[view + 1];
-    ob = ob < 0 ? 0 : (ob > nobs ? nobs : ob);
-    oe = oe < ob ? ob : (oe > nobs ? nobs : oe);
-    const long long cnt = oe - ob;
-    const bool staged = cnt <= (long long)kPoseStageObs;  // workgroup-uniform
+    const ViewObs o = stage_view_observations(a.n_points, a.X, a.offs, view, a.n_obs, a.pt, a.uv,
+                                              s_obs);
     const double qnan = __builtin_nan("");
-
-    // observation j of the view from global memory: the pixel and the gathered
-    // world point, the point NaN when its index is out of range (never
-    // dereferenced) -- a non-finite point or pixel is skipped by accumulate
-    auto gather = [&](long long j, double& X, double& Y, double& Z, double& u, double& v) {
-        const int32_t pi = a.pt[ob + j];
-        u = a.uv[2 * (ob + j)];
-        v = a.uv[2 * (ob + j) + 1];
-        X = Y = Z = qnan;
-        if (pi >= 0 && (size_t)pi < a.n_points) {
-            X = a.X[3 * (size_t)pi];
-            Y = a.X[3 * (size_t)pi + 1];
-            Z = a.X[3 * (size_t)pi + 2];
-        }
-        if (!(__builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z))) X = Y = Z = qnan;
-    };
-    if (staged) {
-        for (long long j = threadIdx.x; j < cnt; j += kBlock) {
-            double X, Y, Z, u, v;
-            gather(j, X, Y, Z, u, v);
-            s_obs[0][j] = X;
-            s_obs[1][j] = Y;
-            s_obs[2][j] = Z;
-            s_obs[3][j] = u;
-            s_obs[4][j] = v;
-        }
-        __syncthreads();
-    }
 
     double ev[12];  // the pose under evaluation: the start pose, then retract(accepted, h)
     {
@@ -2069,7 +1983,7 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
         for (int k = 0; k < 12; ++k) ev[k] = src[k];
     }
 
-    // LM state (lm_core.hpp, P = 6): cur the accepted pose, x the accepted
+    // LM state (batch_solvers.hpp's pieces, P = 6): cur the accepted pose, x the accepted
     // steps summed from 0, A = J^T J (upper triangle), g = J^T r, F, nv at
     // the accepted pose; xn = x + h the step under evaluation.  Between two
     // evaluations the state rests in LDS (it is the same in every lane), so
@@ -2084,39 +1998,18 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
         double acc[kPoseK];
 #pragma unroll
         for (int k = 0; k < kPoseK; ++k) acc[k] = 0.0;
-        for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+        for (long long j = threadIdx.x; j < o.cnt; j += kBlock) {
             double X, Y, Z, ou, ov;
-            if (staged) {
-                X = s_obs[0][j];
-                Y = s_obs[1][j];
-                Z = s_obs[2][j];
-                ou = s_obs[3][j];
-                ov = s_obs[4][j];
-            } else {
-                gather(j, X, Y, Z, ou, ov);
-            }
-            if (!(__builtin_isfinite(ou) && __builtin_isfinite(ov) && __builtin_isfinite(X))) continue;
-            const double px = ev[0] * X + ev[1] * Y + ev[2] * Z + ev[9];
-            const double py = ev[3] * X + ev[4] * Y + ev[5] * Z + ev[10];
-            const double pz = ev[6] * X + ev[7] * Y + ev[8] * Z + ev[11];
+            if (!load_view_observation(o, s_obs, j, X, Y, Z, ou, ov)) continue;
+            double px, py, pz;
+            transform_point(ev, X, Y, Z, px, py, pz);
             double u, v, ju[3], jv[3];
             if (M::template project<false, true, false, true>(c, px, py, pz, u, v, ju, jv) != ST_OK)
                 continue;
             const double r0 = u - ou, r1 = v - ov;
-            const double ja[6] = {ju[0], ju[1], ju[2], py * ju[2] - pz * ju[1],
-                                  pz * ju[0] - px * ju[2], px * ju[1] - py * ju[0]};
-            const double jb[6] = {jv[0], jv[1], jv[2], py * jv[2] - pz * jv[1],
-                                  pz * jv[0] - px * jv[2], px * jv[1] - py * jv[0]};
-            int k = 0;
-#pragma unroll
-            for (int r = 0; r < 6; ++r) {
-#pragma unroll
-                for (int q = r; q < 6; ++q, ++k) acc[k] = fma(ja[r], ja[q], fma(jb[r], jb[q], acc[k]));
-            }
-#pragma unroll
-            for (int r = 0; r < 6; ++r) acc[21 + r] = fma(ja[r], r0, fma(jb[r], r1, acc[21 + r]));
-            acc[27] = fma(r0, r0, fma(r1, r1, acc[27]));
-            acc[28] += 1.0;
+            double ja[6], jb[6];
+            pose_rows(ju, jv, px, py, pz, ja, jb);
+            normal_eq_accumulate<6>(acc, ja, jb, r0, r1);
         }
         block_sum_lds<kPoseK>(acc, s_part, s_tot);
         // from here on every lane holds the same numbers
@@ -2146,7 +2039,7 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
             dmax = 0.0;
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
-                dmax = fmax(dmax, s_tot[pose_ut(k, k)]);
+                dmax = fmax(dmax, s_tot[ut<6>(k, k)]);
                 h[k] = 0.0;
             }
             if (a.max_it == 0) term = 1;
@@ -2157,29 +2050,10 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
             dmax = so[kStDmax];
 #pragma unroll
             for (int k = 0; k < 6; ++k) h[k] = so[kStH + k];
-            // predicted reduction L(0) - L(h) = -(g.h + 0.5 h.A.h)
-            double gh = 0.0, hAh = 0.0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                gh += so[kStG + i] * h[i];
-                double t = 0.0;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) t += so[kStA + pose_ut(i, j)] * h[j];
-                hAh += h[i] * t;
-            }
-            const double pred = -(gh + 0.5 * hAh);
-            const double rho =
-                (__builtin_isfinite(Fn) && pred > 0.0) ? (so[kStF] - Fn) / pred : -1.0;
-            if (rho > 0.0) {
-                accept = true;
-                const double t = 2.0 * rho - 1.0;
-                mu *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-                nu = 2.0;
-            } else {
-                mu *= nu;
-                nu *= 2.0;
-                if (!__builtin_isfinite(mu) || mu > 1e32) term = 2;
-            }
+            const double pred = lm::predicted_reduction<6>(so + kStA, so + kStG, h);
+            const int gain = lm::gain_update(lm::gain_ratio(so[kStF], Fn, pred, true), mu, nu);
+            accept = gain == lm::GAIN_ACCEPT;
+            if (gain == lm::GAIN_FAILED) term = 2;
         }
         // the accepted point after this evaluation: the totals and the pose
         // just evaluated, or the state as it was
@@ -2191,50 +2065,17 @@ __global__ __launch_bounds__(kBlock) void k_pose_batch(CamArg cam, PoseBatchArgs
         for (int k = 0; k < 12; ++k) cur[k] = accept ? ev[k] : so[kStCur + k];
 #pragma unroll
         for (int k = 0; k < 6; ++k) x[k] = !trial ? 0.0 : (accept ? so[kStXn + k] : so[kStX + k]);
-        if (accept && term == 0) {
-            double gi = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) gi = fmax(gi, fabs(gp[k]));
-            if (gi <= a.gtol) term = 1;
-            else if (trial && so[kStF] - Fn <= a.ctol * so[kStF]) term = 1;
-        }
+        if (accept && term == 0 &&
+            lm::accepted_terminates<6>(gp, a.gtol, trial, so[kStF] - Fn, so[kStF], a.ctol))
+            term = 1;
         // advance to the next pose to evaluate, or end
-        bool need = false;
         double xn[6];
-        while (term == 0 && it < a.max_it) {
-            ++it;
-            double Ad[21], mg[6], hs[6];
-#pragma unroll
-            for (int k = 0; k < 21; ++k) Ad[k] = Ap[k];
-            const double floor_d = 1e-12 * fmax(dmax, 1.0);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                Ad[pose_ut(k, k)] += mu * fmax(Ad[pose_ut(k, k)], floor_d);
-                mg[k] = -gp[k];
-            }
-            if (!pose_chol6(Ad, mg, hs)) {
-                mu *= nu;
-                nu *= 2.0;
-                continue;
-            }
-            double hn = 0.0, xnorm = 0.0;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-                xn[k] = x[k] + hs[k];
-                h[k] = xn[k] - x[k];
-                hn += h[k] * h[k];
-                xnorm += x[k] * x[k];
-            }
-            hn = sqrt(hn);
-            xnorm = sqrt(xnorm);
-            if (hn <= a.ptol * (xnorm + a.ptol)) {
-                term = 1;
-                break;
-            }
-            need = true;
-            break;
+        int step = lm::STEP_EXHAUSTED;
+        if (term == 0) {
+            step = lm::next_step<6>(Ap, gp, x, mu, nu, dmax, a.ptol, it, a.max_it, xn, h);
+            if (step == lm::STEP_CONVERGED) term = 1;
         }
-        if (!need) {
+        if (step != lm::STEP_EVALUATE) {
             if (threadIdx.x == 0) {
                 double* dst = reinterpret_cast<double*>(a.poses + view);
 #pragma unroll
@@ -2308,6 +2149,171 @@ __global__ __launch_bounds__(kBlock) void k_p3p(size_t n, const double* __restri
     count[i] = (uint8_t)m;
 }
 
+// ---- the RANSAC core, written for k_pose_estimate and k_relative_pose ----
+// Today k_pose_estimate uses all of it and k_relative_pose only pixel_bearing
+// (and ransac::draw, clamped_range): on stage_records / ransac_select /
+// ransac_fail / write_inlier_mask that kernel returned the same bits but
+// measured 3-7 % slower for DS, so it keeps its own code there.
+// One workgroup per item (a view, a view pair).  Its records -- six planes of
+// doubles, plane 0 NaN marking an unusable one -- are built once, in LDS when
+// the item is short enough, in its own range of six workspace planes
+// otherwise.  Lane l takes hypotheses l, l + 256, ... (ransac::draw), keeps
+// its best ransac::Key, and the workgroup's best under ransac::better wins:
+// the keys with a model all differ, so the result does not depend on the
+// order of the tree.
+struct RansacShared {
+    double score[kBlock];
+    int count[kBlock], h[kBlock], lane[kBlock];
+    double pose[12];
+    unsigned usable;
+};
+
+// The unit bearing of pixel (u, v); false: not usable.  The model's
+// unprojection decides Ok; for UCM the bearing is the projection's inverse
+// (see below).  RADTAN_POLISH: the two-view solver's extra Newton steps.
+template <class TagT, bool RADTAN_POLISH>
+__device__ __forceinline__ bool pixel_bearing(const Cam<double>& c, double u, double v, double& rx,
+                                              double& ry, double& rz) {
+    using M = typename TagT::template type<double>;
+    if (!(__builtin_isfinite(u) && __builtin_isfinite(v))) return false;
+    if (M::unproject(c, u, v, rx, ry, rz) != ST_OK) return false;
+    if constexpr (std::is_same<TagT, Tag<Ucm>>::value) {
+        // Ucm::unproject keeps the reference's denom = 1 - r^2, so its ray is
+        // not the one that projects to (u, v) (off by up to 1.5e-2 rad): a
+        // pose cannot be fitted to such bearings.  The status above decides
+        // usability as for every model; the bearing is the projection's
+        // inverse, denom = 1 + r^2.
+        const double gamma = 1.0 - c.p[4], xi = c.uk[0];  // xi = alpha / gamma
+        const double mx = (u - c.p[2]) / c.p[0] * gamma, my = (v - c.p[3]) / c.p[1] * gamma;
+        const double r2 = mx * mx + my * my;
+        const double coeff = (xi + sqrt(1.0 + (1.0 - xi * xi) * r2)) / (1.0 + r2);
+        rx = coeff * mx;
+        ry = coeff * my;
+        rz = coeff - xi;
+    }
+    if constexpr (RADTAN_POLISH && std::is_same<TagT, Tag<RadTan>>::value) {
+        // RadTan::unproject ends its Newton iteration, as the reference does,
+        // once the distortion residual is below 1e-6, so its ray misses the
+        // direction that projects to (u, v) by up to 1e-6 rad: to a two-view
+        // solver that is noise of 5e-4 px on every exact pixel.  Two more
+        // steps of the same (quadratic) iteration square it away twice.
+        const double k1 = c.p[4], k2 = c.p[5], p1 = c.p[6], p2 = c.p[7], k3 = c.p[8];
+        const double tx = (u - c.p[2]) / c.p[0], ty = (v - c.p[3]) / c.p[1];
+        double x = rx / rz, y = ry / rz;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const double r2 = x * x + y * y, r4 = r2 * r2;
+            const double radial = 1.0 + k1 * r2 + k2 * r4 + k3 * r4 * r2;
+            const double ex = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x) - tx;
+            const double ey = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y - ty;
+            // d(xd, yd) / d(x, y) = [[a00, a01], [a01, a11]] (RadTan::project)
+            const double dr = 2.0 * (k1 + 2.0 * k2 * r2 + 3.0 * k3 * r4);
+            const double a00 = radial + dr * x * x + 2.0 * p1 * y + 6.0 * p2 * x;
+            const double a01 = dr * x * y + 2.0 * p1 * x + 2.0 * p2 * y;
+            const double a11 = radial + dr * y * y + 6.0 * p1 * y + 2.0 * p2 * x;
+            const double det = a00 * a11 - a01 * a01;
+            x -= (a11 * ex - a01 * ey) / det;
+            y -= (a00 * ey - a01 * ex) / det;
+        }
+        rx = x;
+        ry = y;
+        rz = 1.0;
+    }
+    const double nr = sqrt(rx * rx + ry * ry + rz * rz);
+    rx /= nr;
+    ry /= nr;
+    rz /= nr;
+    return __builtin_isfinite(rx) && __builtin_isfinite(ry) && __builtin_isfinite(rz);
+}
+
+// Build the item's cnt records with build(j, r[6]) -> usable, store them
+// (NaN in all six planes when not usable) and count the usable ones; every
+// lane returns the count.
+template <int STAGE, class BuildFn>
+__device__ __forceinline__ unsigned stage_records(long long cnt, bool staged, double* s_rec,
+                                                  double* wrec, size_t wstride, unsigned& s_usable,
+                                                  BuildFn build) {
+    const double qnan = __builtin_nan("");
+    if (threadIdx.x == 0) s_usable = 0u;
+    __syncthreads();
+    unsigned mine = 0;
+    for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+        double r[6];
+        const bool ok = build(j, r);
+        if (ok) ++mine;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            const double v = ok ? r[q] : qnan;
+            if (staged) s_rec[q * STAGE + j] = v;
+            else wrec[q * wstride + j] = v;
+        }
+    }
+    if (mine) atomicAdd(&s_usable, mine);
+    __threadfence_block();
+    __syncthreads();
+    return s_usable;
+}
+
+// The workgroup's best key: every lane brings its own; returns the lane that
+// holds the winner, whose count and score are then in sh.count[0], sh.score[0].
+// s_k: a plane for the solution index, nullptr where a hypothesis has one
+// solution (every key's k is then 0 and costs neither LDS nor a compare).
+template <bool WITH_K>
+__device__ __forceinline__ int ransac_select(RansacShared& sh, int* s_k, const ransac::Key& mine) {
+    const int tid = threadIdx.x;
+    sh.count[tid] = mine.count;
+    sh.score[tid] = mine.score;
+    sh.h[tid] = mine.h;
+    if constexpr (WITH_K) s_k[tid] = mine.k;
+    sh.lane[tid] = tid;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            const int o = tid + off;
+            const ransac::Key k0{sh.count[tid], sh.score[tid], sh.h[tid], WITH_K ? s_k[tid] : 0};
+            const ransac::Key k1{sh.count[o], sh.score[o], sh.h[o], WITH_K ? s_k[o] : 0};
+            if (ransac::better(k1, k0)) {
+                sh.count[tid] = k1.count;
+                sh.score[tid] = k1.score;
+                sh.h[tid] = k1.h;
+                if constexpr (WITH_K) s_k[tid] = k1.k;
+                sh.lane[tid] = sh.lane[o];
+            }
+        }
+        __syncthreads();
+    }
+    return sh.lane[0];
+}
+
+// No pose for item i: NaN pose, the status, the inlier count, a zeroed mask.
+__device__ __forceinline__ void ransac_fail(acm_pose* poses, uint8_t* status, uint32_t* n_inliers,
+                                            uint8_t* mask, size_t i, long long ob, long long cnt,
+                                            uint8_t st, uint32_t n) {
+    const int tid = threadIdx.x;
+    if (tid < 12) reinterpret_cast<double*>(poses + i)[tid] = __builtin_nan("");
+    if (tid == 0) {
+        status[i] = st;
+        n_inliers[i] = n;
+    }
+    if (mask)
+        for (long long j = tid; j < cnt; j += kBlock) mask[ob + j] = 0;
+}
+
+// mask[ob + j] = record j is usable and inlier(six fields of the record)
+template <class InlierFn>
+__device__ __forceinline__ void write_inlier_mask(uint8_t* mask, long long ob, long long cnt,
+                                                  const double* __restrict__ rec, size_t stride,
+                                                  InlierFn inlier) {
+    if (!mask) return;
+    for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+        const double r0 = rec[j];
+        const bool in = __builtin_isfinite(r0) &&
+                        inlier(r0, rec[stride + j], rec[2 * stride + j], rec[3 * stride + j],
+                               rec[4 * stride + j], rec[5 * stride + j]);
+        mask[ob + j] = in ? 1 : 0;
+    }
+}
+
 // acm_pose_estimate_batch: RANSAC over P3P, one workgroup per view.  The
 // view's records (gathered world point and the unit bearing of the pixel, 48
 // B; X = NaN marks an unusable observation) are built once -- in LDS when the
@@ -2337,20 +2343,13 @@ struct PoseEstArgs {
     double cos2;
 };
 
-__device__ __forceinline__ unsigned long long pose_est_mix(unsigned long long z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // the inlier rule at pose P for the record (X, Y, Z, f): the angle between f
 // and R X + t is at most the threshold; e = 1 - cos^2 of it
 __device__ __forceinline__ bool pose_est_inlier(const double (&P)[12], double X, double Y, double Z,
                                                 double fx, double fy, double fz, double cos2,
                                                 double& e) {
-    const double px = P[0] * X + P[1] * Y + P[2] * Z + P[9];
-    const double py = P[3] * X + P[4] * Y + P[5] * Z + P[10];
-    const double pz = P[6] * X + P[7] * Y + P[8] * Z + P[11];
+    double px, py, pz;
+    transform_point(P, X, Y, Z, px, py, pz);
     const double d = fx * px + fy * py + fz * pz;
     const double pp = px * px + py * py + pz * pz;
     if (!(d > 0.0 && d * d >= cos2 * pp)) return false;
@@ -2362,22 +2361,13 @@ template <bool STAGED>
 __device__ __forceinline__ void pose_estimate_view(const PoseEstArgs& a, size_t view, long long ob,
                                                    long long cnt, unsigned usable,
                                                    const double* __restrict__ rec, size_t stride,
-                                                   int (&s_cnt)[kBlock], double (&s_sum)[kBlock],
-                                                   int (&s_hs)[kBlock][2], int (&s_lane)[kBlock],
-                                                   double (&s_pose)[12]) {
+                                                   RansacShared& sh, int (&s_k)[kBlock]) {
     const double qnan = __builtin_nan("");
     const int tid = threadIdx.x;
     double* dst = reinterpret_cast<double*>(a.poses + view);
-    if (usable < 4u) {
-        if (tid < 12) dst[tid] = qnan;
-        if (tid == 0) {
-            a.status[view] = ACM_POSE_EST_TOO_FEW_OBSERVATIONS;
-            a.n_inliers[view] = 0;
-        }
-        if (a.mask)
-            for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
-        return;
-    }
+    if (usable < 4u)
+        return ransac_fail(a.poses, a.status, a.n_inliers, a.mask, view, ob, cnt,
+                           ACM_POSE_EST_TOO_FEW_OBSERVATIONS, 0u);
     // the lane's best: count (-1: no model), score, hypothesis, solution, pose
     int bc = -1, bh = 0, bs = 0;
     double bsum = 0.0, bp[12];
@@ -2387,9 +2377,7 @@ __device__ __forceinline__ void pose_estimate_view(const PoseEstArgs& a, size_t 
         long long i0 = -1, i1 = -1, i2 = -1;
         int got = 0;
         for (int d = 0; d < 8 && got < 3; ++d) {
-            const unsigned long long ctr = 8ull * (unsigned long long)h + (unsigned long long)d + 1ull;
-            const unsigned long long r = pose_est_mix(a.seed + ctr * 0x9E3779B97F4A7C15ull);
-            const long long j = (long long)__umul64hi(r, (unsigned long long)cnt);
+            const long long j = ransac::draw(a.seed, h, d, 8, cnt);
             if (!__builtin_isfinite(rec[j]) || j == i0 || j == i1) continue;
             if (got == 0) i0 = j;
             else if (got == 1) i1 = j;
@@ -2439,160 +2427,60 @@ __device__ __forceinline__ void pose_estimate_view(const PoseEstArgs& a, size_t 
             ++si;
         }
     }
-    s_cnt[tid] = bc;
-    s_sum[tid] = bsum;
-    s_hs[tid][0] = bh;
-    s_hs[tid][1] = bs;
-    s_lane[tid] = tid;
-    __syncthreads();
-    for (int off = kBlock / 2; off > 0; off >>= 1) {
-        if (tid < off) {
-            const int o = tid + off;
-            const int c0 = s_cnt[tid], c1 = s_cnt[o];
-            const double u0 = s_sum[tid], u1 = s_sum[o];
-            const int h0 = s_hs[tid][0], h1 = s_hs[o][0], k0 = s_hs[tid][1], k1 = s_hs[o][1];
-            const bool take = c1 > c0 ||
-                              (c1 == c0 && c1 >= 0 &&
-                               (u1 < u0 || (u1 == u0 && (h1 < h0 || (h1 == h0 && k1 < k0)))));
-            if (take) {
-                s_cnt[tid] = c1;
-                s_sum[tid] = u1;
-                s_hs[tid][0] = h1;
-                s_hs[tid][1] = k1;
-                s_lane[tid] = s_lane[o];
-            }
-        }
-        __syncthreads();
-    }
-    const int best = s_cnt[0], winner = s_lane[0];
-    if (best < a.min_inliers) {  // also no model at all: best = -1
-        if (tid < 12) dst[tid] = qnan;
-        if (tid == 0) {
-            a.status[view] = ACM_POSE_EST_NO_MODEL;
-            a.n_inliers[view] = best < 0 ? 0u : (uint32_t)best;
-        }
-        if (a.mask)
-            for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
-        return;
-    }
+    const int winner = ransac_select<true>(sh, s_k, ransac::Key{bc, bsum, bh, bs});
+    const int best = sh.count[0];
+    if (best < a.min_inliers)  // also no model at all: best = -1
+        return ransac_fail(a.poses, a.status, a.n_inliers, a.mask, view, ob, cnt,
+                           ACM_POSE_EST_NO_MODEL, best < 0 ? 0u : (uint32_t)best);
     if (tid == winner) {
 #pragma unroll
-        for (int q = 0; q < 12; ++q) s_pose[q] = bp[q];
+        for (int q = 0; q < 12; ++q) sh.pose[q] = bp[q];
     }
     __syncthreads();
     double P[12];
 #pragma unroll
-    for (int q = 0; q < 12; ++q) P[q] = s_pose[q];
-    if (tid < 12) dst[tid] = s_pose[tid];
+    for (int q = 0; q < 12; ++q) P[q] = sh.pose[q];
+    if (tid < 12) dst[tid] = sh.pose[tid];
     if (tid == 0) {
         a.status[view] = ACM_POSE_EST_OK;
         a.n_inliers[view] = (uint32_t)best;
     }
-    if (a.mask) {
-        for (long long j = tid; j < cnt; j += kBlock) {
-            const double Xj = rec[j];
-            double e;
-            const bool in = __builtin_isfinite(Xj) &&
-                            pose_est_inlier(P, Xj, rec[stride + j], rec[2 * stride + j],
-                                            rec[3 * stride + j], rec[4 * stride + j],
-                                            rec[5 * stride + j], a.cos2, e);
-            a.mask[ob + j] = in ? 1 : 0;
-        }
-    }
+    write_inlier_mask(a.mask, ob, cnt, rec, stride,
+                      [&](double X, double Y, double Z, double fx, double fy, double fz) {
+                          double e;
+                          return pose_est_inlier(P, X, Y, Z, fx, fy, fz, a.cos2, e);
+                      });
 }
 
 template <class TagT>
 __global__ __launch_bounds__(kBlock) void k_pose_estimate(CamArg cam, PoseEstArgs a) {
-    using M = typename TagT::template type<double>;
     __shared__ double s_rec[6 * kPoseEstStageObs];  // planes X, Y, Z, fx, fy, fz
-    __shared__ double s_sum[kBlock];
-    __shared__ int s_cnt[kBlock];
-    __shared__ int s_hs[kBlock][2];
-    __shared__ int s_lane[kBlock];
-    __shared__ double s_pose[12];
-    __shared__ unsigned s_usable;
+    __shared__ RansacShared sh;
+    __shared__ int s_k[kBlock];  // the keys' solution index (P3P has up to four)
     const Cam<double> c = make_cam<double>(cam);
     const size_t view = blockIdx.x;
-    // the view's observations, clamped into [0, n_obs] (k_pose_batch)
-    const long long nobs = (long long)a.n_obs;
-    long long ob = a.offs[view], oe = a.offs[view + 1];
-    ob = ob < 0 ? 0 : (ob > nobs ? nobs : ob);
-    oe = oe < ob ? ob : (oe > nobs ? nobs : oe);
-    const long long cnt = oe - ob;
+    long long ob, cnt;
+    clamped_range(a.offs, view, a.n_obs, ob, cnt);
     const bool staged = cnt <= (long long)kPoseEstStageObs;  // workgroup-uniform
-    const double qnan = __builtin_nan("");
-    if (threadIdx.x == 0) s_usable = 0u;
-    __syncthreads();
     // the records: j < cnt <= n_obs - ob, so a workspace plane is never overrun
     double* wrec = a.ws + ob;
     const size_t wstride = a.n_obs;
-    unsigned mine = 0;
-    for (long long j = threadIdx.x; j < cnt; j += kBlock) {
-        const int32_t pi = a.pt[ob + j];
-        const double u = a.uv[2 * (ob + j)], v = a.uv[2 * (ob + j) + 1];
-        double X = qnan, Y = qnan, Z = qnan, fx = qnan, fy = qnan, fz = qnan;
-        if (pi >= 0 && (size_t)pi < a.n_points && __builtin_isfinite(u) && __builtin_isfinite(v)) {
-            const double wx = a.X[3 * (size_t)pi], wy = a.X[3 * (size_t)pi + 1],
-                         wz = a.X[3 * (size_t)pi + 2];
-            double rx, ry, rz;
-            if (__builtin_isfinite(wx) && __builtin_isfinite(wy) && __builtin_isfinite(wz) &&
-                M::unproject(c, u, v, rx, ry, rz) == ST_OK) {
-                if constexpr (std::is_same<TagT, Tag<Ucm>>::value) {
-                    // Ucm::unproject keeps the reference's denom = 1 - r^2, so
-                    // its ray is not the one that projects to (u, v) (off by up
-                    // to 1.5e-2 rad): a pose cannot be fitted to such bearings.
-                    // The status above decides usability as for every model;
-                    // the bearing is the projection's inverse, denom = 1 + r^2.
-                    const double gamma = 1.0 - c.p[4], xi = c.uk[0];  // xi = alpha / gamma
-                    const double mx = (u - c.p[2]) / c.p[0] * gamma, my = (v - c.p[3]) / c.p[1] * gamma;
-                    const double r2 = mx * mx + my * my;
-                    const double coeff = (xi + sqrt(1.0 + (1.0 - xi * xi) * r2)) / (1.0 + r2);
-                    rx = coeff * mx;
-                    ry = coeff * my;
-                    rz = coeff - xi;
-                }
-                const double nr = sqrt(rx * rx + ry * ry + rz * rz);
-                rx /= nr;
-                ry /= nr;
-                rz /= nr;
-                if (__builtin_isfinite(rx) && __builtin_isfinite(ry) && __builtin_isfinite(rz)) {
-                    X = wx;
-                    Y = wy;
-                    Z = wz;
-                    fx = rx;
-                    fy = ry;
-                    fz = rz;
-                    ++mine;
-                }
-            }
-        }
-        if (staged) {
-            s_rec[j] = X;
-            s_rec[kPoseEstStageObs + j] = Y;
-            s_rec[2 * kPoseEstStageObs + j] = Z;
-            s_rec[3 * kPoseEstStageObs + j] = fx;
-            s_rec[4 * kPoseEstStageObs + j] = fy;
-            s_rec[5 * kPoseEstStageObs + j] = fz;
-        } else {
-            wrec[j] = X;
-            wrec[wstride + j] = Y;
-            wrec[2 * wstride + j] = Z;
-            wrec[3 * wstride + j] = fx;
-            wrec[4 * wstride + j] = fy;
-            wrec[5 * wstride + j] = fz;
-        }
-    }
-    if (mine) atomicAdd(&s_usable, mine);
-    __threadfence_block();
-    __syncthreads();
-    const unsigned usable = s_usable;
+    const unsigned usable = stage_records<kPoseEstStageObs>(
+        cnt, staged, s_rec, wrec, wstride, sh.usable, [&](long long j, double(&r)[6]) {
+            const int32_t pi = a.pt[ob + j];
+            if (!(pi >= 0 && (size_t)pi < a.n_points)) return false;
+            r[0] = a.X[3 * (size_t)pi];
+            r[1] = a.X[3 * (size_t)pi + 1];
+            r[2] = a.X[3 * (size_t)pi + 2];
+            return __builtin_isfinite(r[0]) && __builtin_isfinite(r[1]) && __builtin_isfinite(r[2]) &&
+                   pixel_bearing<TagT, false>(c, a.uv[2 * (ob + j)], a.uv[2 * (ob + j) + 1], r[3],
+                                              r[4], r[5]);
+        });
     if (threadIdx.x == 0 && a.n_usable) a.n_usable[view] = usable;
     if (staged)
-        pose_estimate_view<true>(a, view, ob, cnt, usable, s_rec, (size_t)kPoseEstStageObs, s_cnt,
-                                 s_sum, s_hs, s_lane, s_pose);
+        pose_estimate_view<true>(a, view, ob, cnt, usable, s_rec, (size_t)kPoseEstStageObs, sh, s_k);
     else
-        pose_estimate_view<false>(a, view, ob, cnt, usable, wrec, wstride, s_cnt, s_sum, s_hs,
-                                  s_lane, s_pose);
+        pose_estimate_view<false>(a, view, ob, cnt, usable, wrec, wstride, sh, s_k);
 }
 
 // -------------------------------------------------- two-view relative pose
@@ -2675,59 +2563,6 @@ struct RelPoseShared {
     int front[4];
     unsigned usable;
 };
-
-// The unit bearing of pixel (u, v): k_pose_estimate's rule, restated so that
-// kernel stays as it is -- the model's unprojection decides Ok, and for UCM
-// the bearing is the projection's inverse (denom = 1 + r^2).
-template <class TagT>
-__device__ __forceinline__ bool relpose_bearing(const Cam<double>& c, double u, double v, double& rx,
-                                                double& ry, double& rz) {
-    using M = typename TagT::template type<double>;
-    if (!(__builtin_isfinite(u) && __builtin_isfinite(v))) return false;
-    if (M::unproject(c, u, v, rx, ry, rz) != ST_OK) return false;
-    if constexpr (std::is_same<TagT, Tag<Ucm>>::value) {
-        const double gamma = 1.0 - c.p[4], xi = c.uk[0];  // xi = alpha / gamma
-        const double mx = (u - c.p[2]) / c.p[0] * gamma, my = (v - c.p[3]) / c.p[1] * gamma;
-        const double r2 = mx * mx + my * my;
-        const double coeff = (xi + sqrt(1.0 + (1.0 - xi * xi) * r2)) / (1.0 + r2);
-        rx = coeff * mx;
-        ry = coeff * my;
-        rz = coeff - xi;
-    }
-    if constexpr (std::is_same<TagT, Tag<RadTan>>::value) {
-        // RadTan::unproject ends its Newton iteration, as the reference does,
-        // once the distortion residual is below 1e-6, so its ray misses the
-        // direction that projects to (u, v) by up to 1e-6 rad: to a two-view
-        // solver that is noise of 5e-4 px on every exact pixel.  Two more
-        // steps of the same (quadratic) iteration square it away twice.
-        const double k1 = c.p[4], k2 = c.p[5], p1 = c.p[6], p2 = c.p[7], k3 = c.p[8];
-        const double tx = (u - c.p[2]) / c.p[0], ty = (v - c.p[3]) / c.p[1];
-        double x = rx / rz, y = ry / rz;
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const double r2 = x * x + y * y, r4 = r2 * r2;
-            const double radial = 1.0 + k1 * r2 + k2 * r4 + k3 * r4 * r2;
-            const double ex = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x) - tx;
-            const double ey = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y - ty;
-            // d(xd, yd) / d(x, y) = [[a00, a01], [a01, a11]] (RadTan::project)
-            const double dr = 2.0 * (k1 + 2.0 * k2 * r2 + 3.0 * k3 * r4);
-            const double a00 = radial + dr * x * x + 2.0 * p1 * y + 6.0 * p2 * x;
-            const double a01 = dr * x * y + 2.0 * p1 * x + 2.0 * p2 * y;
-            const double a11 = radial + dr * y * y + 6.0 * p1 * y + 2.0 * p2 * x;
-            const double det = a00 * a11 - a01 * a01;
-            x -= (a11 * ex - a01 * ey) / det;
-            y -= (a00 * ey - a01 * ex) / det;
-        }
-        rx = x;
-        ry = y;
-        rz = 1.0;
-    }
-    const double nr = sqrt(rx * rx + ry * ry + rz * rz);
-    rx /= nr;
-    ry /= nr;
-    rz /= nr;
-    return __builtin_isfinite(rx) && __builtin_isfinite(ry) && __builtin_isfinite(rz);
-}
 
 // (count, score) of pose P over all usable matches, the lanes striding over
 // the matches and their partial sums added by a fixed tree: every lane
@@ -2865,9 +2700,7 @@ __device__ __forceinline__ void relative_pose_pair(const RelPoseArgs& a, size_t 
         int got = 0;
 #pragma unroll 1
         for (int d = 0; d < 16 && got < 8; ++d) {
-            const unsigned long long ctr = 16ull * (unsigned long long)h + (unsigned long long)d + 1ull;
-            const unsigned long long r = pose_est_mix(a.seed + ctr * 0x9E3779B97F4A7C15ull);
-            const long long j = (long long)__umul64hi(r, (unsigned long long)cnt);
+            const long long j = ransac::draw(a.seed, h, d, 16, cnt);
             if (!__builtin_isfinite(rec[j]) || s.has(j)) continue;
             s.set(got, j);
             ++got;
@@ -2990,12 +2823,8 @@ __global__ __launch_bounds__(kBlock) void k_relative_pose(CamArg cam, RelPoseArg
     __shared__ RelPoseShared sh;
     const Cam<double> c = make_cam<double>(cam);
     const size_t pair = blockIdx.x;
-    // the pair's matches, clamped into [0, n_matches] (k_pose_estimate)
-    const long long nm = (long long)a.n_matches;
-    long long ob = a.offs[pair], oe = a.offs[pair + 1];
-    ob = ob < 0 ? 0 : (ob > nm ? nm : ob);
-    oe = oe < ob ? ob : (oe > nm ? nm : oe);
-    const long long cnt = oe - ob;
+    long long ob, cnt;
+    clamped_range(a.offs, pair, a.n_matches, ob, cnt);
     const bool staged = cnt <= (long long)kRelPoseStage;  // workgroup-uniform
     const double qnan = __builtin_nan("");
     if (threadIdx.x == 0) sh.usable = 0u;
@@ -3007,8 +2836,8 @@ __global__ __launch_bounds__(kBlock) void k_relative_pose(CamArg cam, RelPoseArg
     for (long long j = threadIdx.x; j < cnt; j += kBlock) {
         double f[6];
         const bool ok =
-            relpose_bearing<TagT>(c, a.uv_a[2 * (ob + j)], a.uv_a[2 * (ob + j) + 1], f[0], f[1], f[2]) &&
-            relpose_bearing<TagT>(c, a.uv_b[2 * (ob + j)], a.uv_b[2 * (ob + j) + 1], f[3], f[4], f[5]);
+            pixel_bearing<TagT, true>(c, a.uv_a[2 * (ob + j)], a.uv_a[2 * (ob + j) + 1], f[0], f[1], f[2]) &&
+            pixel_bearing<TagT, true>(c, a.uv_b[2 * (ob + j)], a.uv_b[2 * (ob + j) + 1], f[3], f[4], f[5]);
         if (ok) ++mine;
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
@@ -3087,38 +2916,9 @@ __global__ __launch_bounds__(kBlock) void k_calib_eval(CamArg cam, CalibEvalArgs
     const Cam<double> c = make_cam<double>(cam);
     const size_t view = blockIdx.x;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    // the view's observations, clamped into [0, n_obs] (k_pose_batch)
-    const long long nobs = (long long)a.n_obs;
-    long long ob = a.offs[view], oe = a.offs[view + 1];
-    ob = ob < 0 ? 0 : (ob > nobs ? nobs : ob);
-    oe = oe < ob ? ob : (oe > nobs ? nobs : oe);
-    const long long cnt = oe - ob;
-    const bool staged = cnt <= (long long)kPoseStageObs;  // workgroup-uniform
-    const double qnan = __builtin_nan("");
-    auto gather = [&](long long j, double& X, double& Y, double& Z, double& u, double& v) {
-        const int32_t pi = a.pt[ob + j];
-        u = a.uv[2 * (ob + j)];
-        v = a.uv[2 * (ob + j) + 1];
-        X = Y = Z = qnan;
-        if (pi >= 0 && (size_t)pi < a.n_points) {
-            X = a.X[3 * (size_t)pi];
-            Y = a.X[3 * (size_t)pi + 1];
-            Z = a.X[3 * (size_t)pi + 2];
-        }
-        if (!(__builtin_isfinite(X) && __builtin_isfinite(Y) && __builtin_isfinite(Z))) X = Y = Z = qnan;
-    };
-    if (staged) {
-        for (long long j = threadIdx.x; j < cnt; j += kBlock) {
-            double X, Y, Z, u, v;
-            gather(j, X, Y, Z, u, v);
-            s_obs[0][j] = X;
-            s_obs[1][j] = Y;
-            s_obs[2][j] = Z;
-            s_obs[3][j] = u;
-            s_obs[4][j] = v;
-        }
-        __syncthreads();
-    }
+    const ViewObs o = stage_view_observations(a.n_points, a.X, a.offs, view, a.n_obs, a.pt, a.uv,
+                                              s_obs);
+    const long long cnt = o.cnt;
     double ev[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) ev[k] = a.poses[12 * view + k];
@@ -3136,33 +2936,14 @@ __global__ __launch_bounds__(kBlock) void k_calib_eval(CamArg cam, CalibEvalArgs
         bool ok = false;
         if (j < cnt) {
             double X, Y, Z, ou, ov;
-            if (staged) {
-                X = s_obs[0][j];
-                Y = s_obs[1][j];
-                Z = s_obs[2][j];
-                ou = s_obs[3][j];
-                ov = s_obs[4][j];
-            } else {
-                gather(j, X, Y, Z, ou, ov);
-            }
-            if (__builtin_isfinite(ou) && __builtin_isfinite(ov) && __builtin_isfinite(X)) {
-                const double px = ev[0] * X + ev[1] * Y + ev[2] * Z + ev[9];
-                const double py = ev[3] * X + ev[4] * Y + ev[5] * Z + ev[10];
-                const double pz = ev[6] * X + ev[7] * Y + ev[8] * Z + ev[11];
+            if (load_view_observation(o, s_obs, j, X, Y, Z, ou, ov)) {
+                double px, py, pz;
+                transform_point(ev, X, Y, Z, px, py, pz);
                 double u, v, ju[P + 3], jv[P + 3];
                 if (M::template project<true, true, false, true>(c, px, py, pz, u, v, ju, jv) ==
                     ST_OK) {
                     ok = true;
-                    const double* qu = ju + P;
-                    const double* qv = jv + P;
-                    ru[0] = qu[0]; ru[1] = qu[1]; ru[2] = qu[2];
-                    ru[3] = py * qu[2] - pz * qu[1];
-                    ru[4] = pz * qu[0] - px * qu[2];
-                    ru[5] = px * qu[1] - py * qu[0];
-                    rv[0] = qv[0]; rv[1] = qv[1]; rv[2] = qv[2];
-                    rv[3] = py * qv[2] - pz * qv[1];
-                    rv[4] = pz * qv[0] - px * qv[2];
-                    rv[5] = px * qv[1] - py * qv[0];
+                    pose_rows(ju + P, jv + P, px, py, pz, ru, rv);
 #pragma unroll
                     for (int k = 0; k < P; ++k) {
                         ru[6 + k] = ju[k];
@@ -3297,7 +3078,7 @@ __global__ __launch_bounds__(64) void k_calib_totals(CalibStepArgs a, const doub
 
 // Per participating view, 16 lanes: lane q solves (App + damping) y = column q
 // of the view's system for the intrinsics' columns and the residual's
-// (pose_chol6; every lane factors the same 6 x 6), then multiplies by Atp.
+// (chol_ut<6>; every lane factors the same 6 x 6), then multiplies by Atp.
 __global__ __launch_bounds__(64) void k_calib_schur(CalibStepArgs a, double mu, double floor_d) {
     const size_t view = (size_t)blockIdx.x * 4 + (threadIdx.x >> 4);
     const int q = threadIdx.x & 15;
@@ -3314,11 +3095,11 @@ __global__ __launch_bounds__(64) void k_calib_schur(CalibStepArgs a, double mu, 
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
 #pragma unroll
-        for (int cidx = r; cidx < 6; ++cidx) A[pose_ut(r, cidx)] = S[r * kCalN + cidx];
-        A[pose_ut(r, r)] += mu * fmax(A[pose_ut(r, r)], floor_d);
+        for (int cidx = r; cidx < 6; ++cidx) A[ut<6>(r, cidx)] = S[r * kCalN + cidx];
+        A[ut<6>(r, r)] += mu * fmax(A[ut<6>(r, r)], floor_d);
         b[r] = S[r * kCalN + q];
     }
-    const bool ok = pose_chol6(A, b, x);
+    const bool ok = chol_ut<6>(A, b, x);
     if (q == kCalN - 1) a.bad[view] = ok ? 0u : 1u;
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
@@ -6710,6 +6491,23 @@ static int check_layout(int layout) {
     return ACM_SUCCESS;
 }
 
+// the LM fields every batched solver's config and kernel arguments share
+template <class Args, class Cfg>
+static void lm_args_from(Args& a, const Cfg& cfg) {
+    a.max_it = cfg.max_iterations;
+    a.ctol = cfg.cost_tolerance;
+    a.ptol = cfg.parameter_tolerance;
+    a.gtol = cfg.gradient_tolerance;
+    a.mu0 = cfg.initial_damping;
+}
+
+// what the two RANSAC configs share; min_sample: the solver's sample size
+template <class Cfg>
+static bool ransac_config_ok(const Cfg& cfg, int min_sample) {
+    return cfg.n_hypotheses >= 1 && cfg.n_hypotheses <= 65536 && cfg.flags == 0 &&
+           cfg.inlier_angle > 0.0 && cfg.inlier_angle < kPi / 2.0 && cfg.min_inliers >= min_sample;
+}
+
 }  // namespace acm
 
 using namespace acm;
@@ -7341,12 +7139,8 @@ ACM_API int acm_triangulate(const acm_camera* cam, size_t n_views, const acm_pos
         a.cost = cost;
         a.n_valid = n_valid;
         a.info = information;
-        a.max_it = cfg->max_iterations;
+        lm_args_from(a, *cfg);
         a.flags = cfg->flags;
-        a.ctol = cfg->cost_tolerance;
-        a.ptol = cfg->parameter_tolerance;
-        a.gtol = cfg->gradient_tolerance;
-        a.mu0 = cfg->initial_damping;
         a.sin2 = cfg->min_parallax_sin2;
         const unsigned nb = (unsigned)((n_points + kBlock - 1) / kBlock);
         hipLaunchKernelGGL(k_triangulate<TagT>, dim3(nb), dim3(kBlock), 0, s,
@@ -7407,11 +7201,7 @@ ACM_API int acm_pose_optimize_batch(const acm_camera* cam, size_t n_views, acm_p
         a.n_valid = n_valid;
         a.iters = iterations;
         a.info = information;
-        a.max_it = cfg->max_iterations;
-        a.ctol = cfg->cost_tolerance;
-        a.ptol = cfg->parameter_tolerance;
-        a.gtol = cfg->gradient_tolerance;
-        a.mu0 = cfg->initial_damping;
+        lm_args_from(a, *cfg);
         hipLaunchKernelGGL(k_pose_batch<TagT>, dim3((unsigned)n_views), dim3(kBlock), 0, s,
                            prep(*cam), a);
         return check_launch("acm_pose_optimize_batch");
@@ -7457,8 +7247,7 @@ ACM_API int acm_pose_estimate_batch(const acm_camera* cam, size_t n_views, acm_p
     int rc = check_cam(cam);
     if (rc) return rc;
     if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
-    if (cfg->n_hypotheses < 1 || cfg->n_hypotheses > 65536 || cfg->flags != 0 ||
-        !(cfg->inlier_angle > 0.0 && cfg->inlier_angle < kPi / 2.0) || cfg->min_inliers < 4)
+    if (!ransac_config_ok(*cfg, 4))
         return fail(ACM_ERR_INVALID_ARGUMENT,
                     "n_hypotheses outside 1 .. 65536, nonzero flags, inlier_angle outside (0, pi/2) "
                     "or min_inliers < 4");
@@ -7537,9 +7326,7 @@ ACM_API int acm_relative_pose_batch(const acm_camera* cam, size_t n_pairs, acm_p
     int rc = check_cam(cam);
     if (rc) return rc;
     if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
-    if (cfg->n_hypotheses < 1 || cfg->n_hypotheses > 65536 || cfg->flags != 0 ||
-        !(cfg->inlier_angle > 0.0 && cfg->inlier_angle < kPi / 2.0) || cfg->min_inliers < 8 ||
-        cfg->refit_rounds < 0 || cfg->refit_rounds > 8)
+    if (!ransac_config_ok(*cfg, 8) || cfg->refit_rounds < 0 || cfg->refit_rounds > 8)
         return fail(ACM_ERR_INVALID_ARGUMENT,
                     "n_hypotheses outside 1 .. 65536, nonzero flags, inlier_angle outside (0, pi/2), "
                     "min_inliers < 8 or refit_rounds outside 0 .. 8");
@@ -7832,23 +7619,18 @@ ACM_API int acm_calibrate(acm_camera* cam, size_t n_views, acm_pose* poses, size
         }
         ++evals;
         const double Fn = ht[0], nvn = ht[1], pred = ht[2];
-        const double rho =
-            (std::isfinite(Fn) && pred > 0.0 && nvn >= nv) ? (F - Fn) / pred : -1.0;
-        if (rho > 0.0) {
+        // a trial that lost valid observations is rejected (k_triangulate's rule)
+        const int gain = lm::gain_update(lm::gain_ratio(F, Fn, pred, nvn >= nv), mu, nu);
+        if (gain == lm::GAIN_ACCEPT) {
             const double dF = F - Fn, Fold = F;
             cur ^= 1;
             for (int i = 0; i < P; ++i) x[i] = xn[i];
             F = Fn;
             nv = nvn;
-            const double t = 2.0 * rho - 1.0;
-            mu *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-            nu = 2.0;
             if (ginf() <= cfg->gradient_tolerance) term = ACM_LM_GRADIENT;
             else if (dF <= cfg->cost_tolerance * Fold) term = ACM_LM_COST;
-        } else {
-            mu *= nu;
-            nu *= 2.0;
-            if (!std::isfinite(mu) || mu > 1e32) term = ACM_LM_FAILED;
+        } else if (gain == lm::GAIN_FAILED) {
+            term = ACM_LM_FAILED;
         }
     }
 

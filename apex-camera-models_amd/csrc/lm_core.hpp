@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "acm.h"
+#include "batch_solvers.hpp"  // gain_ratio, gain_update: the arithmetic shared with the device LMs
 
 namespace acm {
 namespace lm {
@@ -155,27 +156,20 @@ inline int consume(State& s, const acm_lm_config& cfg, const double* res,
         hAh += s.h[i] * t;
     }
     const double pred = -(gh + 0.5 * hAh);
-    const double rho = (isfinite(Fn) && pred > 0.0) ? (s.F - Fn) / pred : -1.0;
-    if (rho > 0.0) {
-        const double dF = s.F - Fn;
-        const double Fold = s.F;
+    const double rho = gain_ratio(s.F, Fn, pred, true);
+    const double dF = s.F - Fn, Fold = s.F;
+    const int gain = gain_update(rho, s.mu, s.nu);
+    if (gain == GAIN_ACCEPT) {
         for (int i = 0; i < P; ++i) s.x[i] = s.xn[i];
         for (int i = 0; i < P * P; ++i) s.A[i] = An[i];
         for (int i = 0; i < P; ++i) s.g[i] = gn[i];
         s.F = Fn;
         s.nv = nvn;
-        const double t = 2.0 * rho - 1.0;
-        s.mu *= fmax(1.0 / 3.0, 1.0 - t * t * t);
-        s.nu = 2.0;
         if (ginf(P, s.g) <= cfg.gradient_tolerance) s.term = ACM_LM_GRADIENT;
         else if (dF <= cfg.cost_tolerance * Fold) s.term = ACM_LM_COST;
-    } else {
-        s.mu *= s.nu;
-        s.nu *= 2.0;
-        if (!isfinite(s.mu) || s.mu > 1e32) {
-            s.term = ACM_LM_FAILED;
-            return DONE;
-        }
+    } else if (gain == GAIN_FAILED) {
+        s.term = ACM_LM_FAILED;
+        return DONE;
     }
     return advance(s, cfg, P);
 }
