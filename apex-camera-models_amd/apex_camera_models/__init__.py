@@ -23,6 +23,8 @@ from .optimizer import (PoseEstimateConfig, PoseEstimateResult, estimate_poses, 
                         p3p)
 from .optimizer import (RelativePoseConfig, RelativePoseResult,  # noqa: E402
                         estimate_relative_poses, relative_pose_8pt, two_view_tracks)
+from .optimizer import (HomographyConfig, HomographyResult,  # noqa: E402
+                        estimate_homographies, homography_4pt)
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
@@ -35,4 +37,5 @@ __all__ = [
     "PoseEstimateConfig", "PoseEstimateResult", "estimate_poses", "p3p",
     "RelativePoseConfig", "RelativePoseResult", "estimate_relative_poses", "relative_pose_8pt",
     "two_view_tracks",
+    "HomographyConfig", "HomographyResult", "estimate_homographies", "homography_4pt",
 ]

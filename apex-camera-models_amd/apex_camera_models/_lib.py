@@ -165,6 +165,23 @@ RELPOSE_OK, RELPOSE_TOO_FEW_MATCHES, RELPOSE_NO_MODEL = 0, 1, 2
 RELPOSE_STAGE_MATCHES = 1024
 
 
+class HomographyConfig(ctypes.Structure):
+    """acm_homography_config (include/acm.h)."""
+    _fields_ = [
+        ("n_hypotheses", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("inlier_angle", ctypes.c_double),
+        ("min_inliers", ctypes.c_int32),
+        ("refit_rounds", ctypes.c_int32),
+    ]
+
+
+# acm_homography_status / the per-pair LDS staging budget (include/acm.h)
+HOMOGRAPHY_OK, HOMOGRAPHY_TOO_FEW_MATCHES, HOMOGRAPHY_NO_MODEL = 0, 1, 2
+HOMOGRAPHY_STAGE_MATCHES = 1024
+
+
 class CalibrateConfig(ctypes.Structure):
     """acm_calibrate_config (include/acm.h)."""
     _fields_ = [
@@ -291,6 +308,10 @@ EXPORTED_SYMBOLS = (
     "acm_relative_pose_batch_default_config",
     "acm_relative_pose_batch_workspace_size",
     "acm_relative_pose_batch",
+    "acm_homography_4pt",
+    "acm_homography_batch_default_config",
+    "acm_homography_batch_workspace_size",
+    "acm_homography_batch",
     "acm_calibrate_default_config",
     "acm_calibrate_workspace_size",
     "acm_calibrate",
@@ -509,6 +530,20 @@ def load():
     L.acm_relative_pose_batch.argtypes = [cam_p, sz, vp, vp, sz, vp, vp, rp_p, vp, vp, vp, vp, vp,
                                           sz, vp]
     L.acm_relative_pose_batch.restype = i
+    # n, bearings_a, bearings_b, homography, poses, planes, translation, count, n_front, stream
+    L.acm_homography_4pt.argtypes = [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.acm_homography_4pt.restype = i
+    hg_p = ctypes.POINTER(HomographyConfig)
+    L.acm_homography_batch_default_config.argtypes = [hg_p]
+    L.acm_homography_batch_default_config.restype = None
+    L.acm_homography_batch_workspace_size.argtypes = [sz, sz]
+    L.acm_homography_batch_workspace_size.restype = sz
+    # cam, n_pairs, pair_offsets, n_matches, uv_a, uv_b, cfg, homography, status, n_inliers,
+    # poses, planes, n_solutions, n_front, translation, mask, n_usable, workspace,
+    # workspace_bytes, stream
+    L.acm_homography_batch.argtypes = [cam_p, sz, vp, sz, vp, vp, hg_p, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, vp, vp, vp, sz, vp]
+    L.acm_homography_batch.restype = i
     cal_p =ctypes.POINTER(CalibrateConfig)
     L.acm_calibrate_default_config.argtypes = [cal_p]
     L.acm_calibrate_default_config.restype = None

@@ -689,6 +689,128 @@ def two_view_tracks(pair_offsets, uv_a, uv_b, inlier_mask, poses=None):
     return view_poses, track_offsets, obs_view, obs_uv, match
 
 
+# ------------------------------------------------------- two-view homography
+def homography_4pt(bearings_a, bearings_b):
+    """The 4-point homography solver (acm_homography_4pt), batched:
+    bearings_a, bearings_b (N, 4, 3), the rays of four matches in image A and
+    in image B, any length.  Returns (homography (N, 9) f64 -- f_b ~ H f_a,
+    row-major, middle singular value 1 --, poses (N, 2, 12) f64 -- the two
+    motions p_b = R p_a + t, unit t --, planes (N, 2, 4) f64 -- (n, d / |t|)
+    --, translation (N,) f64 -- tau = |t| / d --, count (N,) u8 -- 0, 1
+    (rotation only) or 2 --, n_front (N, 2) u8) on the device; NaN and 0 where
+    it fails and in the slots beyond count."""
+    L = _lib.load()
+    fa = _as_device_f64(torch.as_tensor(bearings_a).reshape(-1, 3), 3)
+    fb = _as_device_f64(torch.as_tensor(bearings_b).reshape(-1, 3), 3)
+    if fa.shape[0] % 4 or fa.shape[0] != fb.shape[0]:
+        raise ValueError("bearings_a and bearings_b must both be (N, 4, 3)")
+    n = fa.shape[0] // 4
+    hom = torch.empty((n, 9), dtype=torch.float64, device="cuda")
+    poses = torch.empty((n, 2, 12), dtype=torch.float64, device="cuda")
+    planes = torch.empty((n, 2, 4), dtype=torch.float64, device="cuda")
+    tau = torch.empty((n,), dtype=torch.float64, device="cuda")
+    count = torch.empty((n,), dtype=torch.uint8, device="cuda")
+    front = torch.empty((n, 2), dtype=torch.uint8, device="cuda")
+    ptr = [x.data_ptr() if n else None for x in (fa, fb, hom, poses, planes, tau, count, front)]
+    _lib.check(L.acm_homography_4pt(n, *ptr, _stream_handle()))
+    return hom, poses, planes, tau, count, front
+
+
+@dataclass
+class HomographyConfig:
+    """acm_homography_config; the defaults are
+    acm_homography_batch_default_config's, except inlier_angle: None takes the
+    angle of estimate_homographies' threshold_px."""
+    n_hypotheses: int = 256
+    seed: int = 1
+    inlier_angle: Optional[float] = None
+    min_inliers: int = 4
+    refit_rounds: int = 3
+
+
+@dataclass
+class HomographyResult:
+    """Device tensors, K pairs: homography (K, 9) f64 (f_b ~ H f_a, row-major,
+    middle singular value 1; NaN where status is not HOMOGRAPHY_OK), status
+    (K,) u8 (_lib.HOMOGRAPHY_OK / HOMOGRAPHY_TOO_FEW_MATCHES /
+    HOMOGRAPHY_NO_MODEL), n_inliers (K,) i32, poses (K, 2, 12) f64 (the two
+    motions camera A -> camera B, R row-major, then the unit t; NaN beyond
+    n_solutions), planes (K, 2, 4) f64 ((n, d / |t|) in camera A's frame),
+    n_solutions (K,) u8 (1: rotation only, t = 0), n_front (K, 2) i32,
+    translation (K,) f64 (tau = |t| / d), inlier_mask (M,) u8, n_usable (K,)
+    i32."""
+    homography: torch.Tensor
+    status: torch.Tensor
+    n_inliers: torch.Tensor
+    poses: torch.Tensor
+    planes: torch.Tensor
+    n_solutions: torch.Tensor
+    n_front: torch.Tensor
+    translation: torch.Tensor
+    inlier_mask: torch.Tensor
+    n_usable: torch.Tensor
+
+    def pose_slot(self, slot):
+        """(K, 12): one solution per pair as two_view_tracks' poses.  slot: an
+        int for all pairs, or (K,) integers (0 or 1) choosing per pair."""
+        if isinstance(slot, int):
+            return self.poses[:, slot].contiguous()
+        idx = torch.as_tensor(slot).to(device=self.poses.device, dtype=torch.int64).reshape(-1, 1, 1)
+        return torch.gather(self.poses, 1, idx.expand(-1, 1, 12)).reshape(-1, 12).contiguous()
+
+
+def estimate_homographies(model: CameraModel, pair_offsets, uv_a, uv_b,
+                          config: Optional[HomographyConfig] = None,
+                          threshold_px: float = 3.0) -> HomographyResult:
+    """Every view pair's homography from 2-D / 2-D matches
+    (acm_homography_batch): the model of a planar scene or a rotating camera,
+    where estimate_relative_poses' 8-point system loses rank.  The 4-point
+    solver on the unprojected rays inside RANSAC with a refit over the
+    inliers, one workgroup per pair, all pairs in one launch; the final H is
+    decomposed into its two (R, t, plane).  Inputs as estimate_relative_poses.
+    Without config.inlier_angle the threshold is atan(threshold_px / min(fx,
+    fy))."""
+    import math
+    L = _lib.load()
+    offs = torch.as_tensor(pair_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    ua = _as_device_f64(uv_a, 2)
+    ub = _as_device_f64(uv_b, 2)
+    k, m = offs.shape[0] - 1, ua.shape[0]
+    if k < 0 or ub.shape[0] != m:
+        raise ValueError("pair_offsets needs K + 1 entries; uv_a and uv_b one row per match")
+    cam = model.acm_camera()
+    c = config or HomographyConfig()
+    cfg = _lib.HomographyConfig()
+    L.acm_homography_batch_default_config(ctypes.byref(cfg))
+    cfg.n_hypotheses = c.n_hypotheses
+    cfg.seed = c.seed
+    cfg.min_inliers = c.min_inliers
+    cfg.refit_rounds = c.refit_rounds
+    cfg.inlier_angle = (c.inlier_angle if c.inlier_angle is not None
+                        else math.atan(threshold_px / min(cam.params[0], cam.params[1])))
+    hom = torch.empty((k, 9), dtype=torch.float64, device="cuda")
+    status = torch.empty((k,), dtype=torch.uint8, device="cuda")
+    n_inliers = torch.empty((k,), dtype=torch.int32, device="cuda")
+    poses = torch.empty((k, 2, 12), dtype=torch.float64, device="cuda")
+    planes = torch.empty((k, 2, 4), dtype=torch.float64, device="cuda")
+    n_solutions = torch.empty((k,), dtype=torch.uint8, device="cuda")
+    n_front = torch.empty((k, 2), dtype=torch.int32, device="cuda")
+    tau = torch.empty((k,), dtype=torch.float64, device="cuda")
+    n_usable = torch.empty((k,), dtype=torch.int32, device="cuda")
+    mask = torch.zeros((m,), dtype=torch.uint8, device="cuda")  # entries no pair owns stay 0
+    ws_bytes = L.acm_homography_batch_workspace_size(k, m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device="cuda")
+    per_pair = [x.data_ptr() if k else None
+                for x in (hom, status, n_inliers, poses, planes, n_solutions, n_front, tau)]
+    _lib.check(L.acm_homography_batch(
+        ctypes.byref(cam), k, offs.data_ptr(), m, ua.data_ptr() if m else None,
+        ub.data_ptr() if m else None, ctypes.byref(cfg), *per_pair,
+        mask.data_ptr() if m else None, n_usable.data_ptr() if k else None, ws.data_ptr(),
+        ws_bytes, _stream_handle()))
+    return HomographyResult(hom, status, n_inliers, poses, planes, n_solutions, n_front, tau, mask,
+                            n_usable)
+
+
 # ------------------------------------------------------ multi-view calibration
 @dataclass
 class CalibrationConfig:

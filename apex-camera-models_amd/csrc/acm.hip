@@ -36,6 +36,7 @@
 #include "lm_doorbell.hpp"
 #include "p3p.hpp"
 #include "essential.hpp"
+#include "homography.hpp"
 
 namespace acm {
 
@@ -2855,6 +2856,370 @@ __global__ __launch_bounds__(kBlock) void k_relative_pose(CamArg cam, RelPoseArg
         relative_pose_pair<true>(a, pair, ob, cnt, usable, s_rec, (size_t)kRelPoseStage, sh);
     else
         relative_pose_pair<false>(a, pair, ob, cnt, usable, wrec, wstride, sh);
+}
+
+// ------------------------------------------------------ two-view homography
+// acm_homography_4pt: one lane per problem, homography.hpp's solver
+// (registers only).
+__global__ __launch_bounds__(kBlock) void k_homography_4pt(
+    size_t n, const double* __restrict__ fa, const double* __restrict__ fb,
+    double* __restrict__ hom, acm_pose* __restrict__ poses, double* __restrict__ planes,
+    double* __restrict__ translation, uint8_t* __restrict__ count, uint8_t* __restrict__ n_front) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double H[9], P[24], Q[8], tau;
+    unsigned front[2];
+    const int c = homography::solve(4, fa + 12 * i, fb + 12 * i, H, P, Q, &tau, front);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) hom[9 * i + q] = H[q];
+    double* dst = reinterpret_cast<double*>(poses + 2 * i);
+#pragma unroll
+    for (int q = 0; q < 24; ++q) dst[q] = P[q];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) planes[8 * i + q] = Q[q];
+    if (translation) translation[i] = tau;
+    count[i] = (uint8_t)c;
+    n_front[2 * i] = (uint8_t)front[0];
+    n_front[2 * i + 1] = (uint8_t)front[1];
+}
+
+// acm_homography_batch: RANSAC over the 4-point solver, one workgroup per
+// view pair, on the shared core (stage_records, ransac_select,
+// write_inlier_mask) with k_relative_pose's records.  A hypothesis' model is
+// the normalised H; the refit rounds and the one decomposition at the end run
+// with the whole workgroup on one model.
+constexpr int kHomStage = ACM_HOMOGRAPHY_STAGE_MATCHES;  // per pair; 48 B each
+
+struct HomArgs {
+    size_t n_matches;
+    const int64_t* offs;
+    const double* uv_a;
+    const double* uv_b;
+    double* hom;
+    uint8_t* status;
+    uint32_t* n_inliers;
+    acm_pose* poses;
+    double* planes;
+    uint8_t* n_solutions;
+    uint32_t* n_front;
+    double* translation;
+    uint8_t* mask;
+    uint32_t* n_usable;
+    double* ws;  // six planes of n_matches doubles
+    int H, min_inliers, refit_rounds;
+    unsigned long long seed;
+    double sin2;
+};
+
+// the four local indices of a sample, in named fields (see RelPoseSample)
+struct HomSample {
+    long long j0 = -1, j1 = -1, j2 = -1, j3 = -1;
+    __device__ __forceinline__ bool has(long long j) const {
+        return j == j0 || j == j1 || j == j2 || j == j3;
+    }
+    __device__ __forceinline__ void set(int q, long long j) {
+        j0 = q == 0 ? j : j0;
+        j1 = q == 1 ? j : j1;
+        j2 = q == 2 ? j : j2;
+        j3 = q == 3 ? j : j3;
+    }
+    __device__ __forceinline__ long long get(int q) const {
+        return q == 0 ? j0 : q == 1 ? j1 : q == 2 ? j2 : j3;
+    }
+};
+
+// what the refit rounds share through LDS beside RansacShared
+struct HomShared {
+    double factor[kBlock / 64][essential::kTri];
+    double model[9];
+};
+
+// ransac_fail's sibling for a pair without a homography
+__device__ __forceinline__ void hom_fail(const HomArgs& a, size_t pair, long long ob, long long cnt,
+                                         uint8_t st, uint32_t n) {
+    const int tid = threadIdx.x;
+    const double qnan = __builtin_nan("");
+    if (tid < 9) a.hom[9 * pair + tid] = qnan;
+    if (a.poses && tid < 24) reinterpret_cast<double*>(a.poses + 2 * pair)[tid] = qnan;
+    if (a.planes && tid < 8) a.planes[8 * pair + tid] = qnan;
+    if (a.n_front && tid < 2) a.n_front[2 * pair + tid] = 0u;
+    if (tid == 0) {
+        a.status[pair] = st;
+        a.n_inliers[pair] = n;
+        if (a.n_solutions) a.n_solutions[pair] = 0;
+        if (a.translation) a.translation[pair] = qnan;
+    }
+    if (a.mask)
+        for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
+}
+
+// The workgroup's sums of (i0, i1, d) by a fixed tree through sh.count, sh.h
+// and sh.score: every lane returns the same three.  Ends with a barrier after
+// the last read of sh.
+__device__ __forceinline__ void hom_reduce(RansacShared& sh, int& i0, int& i1, double& d) {
+    const int tid = threadIdx.x;
+    sh.count[tid] = i0;
+    sh.h[tid] = i1;
+    sh.score[tid] = d;
+    __syncthreads();
+    for (int off = kBlock / 2; off > 0; off >>= 1) {
+        if (tid < off) {
+            sh.count[tid] += sh.count[tid + off];
+            sh.h[tid] += sh.h[tid + off];
+            sh.score[tid] += sh.score[tid + off];
+        }
+        __syncthreads();
+    }
+    i0 = sh.count[0];
+    i1 = sh.h[0];
+    d = sh.score[0];
+    __syncthreads();
+}
+
+// (count, score) of the model H over all usable matches, the lanes striding
+// over the matches
+__device__ __forceinline__ void hom_score(const double (&H)[9], const double* __restrict__ rec,
+                                          size_t stride, long long cnt, double sin2,
+                                          RansacShared& sh, int& count, double& score) {
+    int c = 0, none = 0;
+    double sum = 0.0;
+    for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+        const double ax = rec[j];
+        double e;
+        if (__builtin_isfinite(ax) &&
+            homography::inlier(H, ax, rec[stride + j], rec[2 * stride + j], rec[3 * stride + j],
+                               rec[4 * stride + j], rec[5 * stride + j], sin2, e)) {
+            ++c;
+            sum += e;
+        }
+    }
+    hom_reduce(sh, c, none, sum);
+    count = c;
+    score = sum;
+}
+
+// One refit round on the model H: the factor of its inliers' rows (the
+// butterfly of relpose_refit), the normalised result Q signed by the majority
+// of those inliers.  false (workgroup-uniform): no finite result.
+__device__ __forceinline__ bool hom_refit(const double (&H)[9], const double* __restrict__ rec,
+                                          size_t stride, long long cnt, double sin2,
+                                          RansacShared& sh, HomShared& hs, double (&Q)[9]) {
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    double T[essential::kTri];
+    essential::clear(T);
+#pragma unroll 1
+    for (long long j = tid; j < cnt; j += kBlock) {
+        const double fa[3] = {rec[j], rec[stride + j], rec[2 * stride + j]};
+        const double fb[3] = {rec[3 * stride + j], rec[4 * stride + j], rec[5 * stride + j]};
+        double e;
+        if (!(__builtin_isfinite(fa[0]) &&
+              homography::inlier(H, fa[0], fa[1], fa[2], fb[0], fb[1], fb[2], sin2, e)))
+            continue;
+        homography::feed_match(T, fa, fb);
+    }
+    // wave merge (fixed butterfly order), then the four waves' factors in order
+#pragma unroll 1
+    for (int off = 32; off > 0; off >>= 1) {
+        double O[essential::kTri];
+#pragma unroll
+        for (int q = 0; q < essential::kTri; ++q) O[q] = __shfl_down(T[q], off, 64);
+        if (lane < off) essential::merge(T, O);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < essential::kTri; ++q) hs.factor[wid][q] = T[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < essential::kTri; ++q) T[q] = hs.factor[0][q];
+#pragma unroll 1
+    for (int w = 1; w < kBlock / 64; ++w) {
+        double O[essential::kTri];
+#pragma unroll
+        for (int q = 0; q < essential::kTri; ++q) O[q] = hs.factor[w][q];
+        essential::merge(T, O);
+    }
+    // every lane holds the same factor and runs the same solve
+    const bool ok = homography::factor_to_h(T, Q);
+    int sgn = 0, none = 0;
+    double unused = 0.0;
+    if (ok) {
+        for (long long j = tid; j < cnt; j += kBlock) {
+            const double fa[3] = {rec[j], rec[stride + j], rec[2 * stride + j]};
+            const double fb[3] = {rec[3 * stride + j], rec[4 * stride + j], rec[5 * stride + j]};
+            double e;
+            if (__builtin_isfinite(fa[0]) &&
+                homography::inlier(H, fa[0], fa[1], fa[2], fb[0], fb[1], fb[2], sin2, e))
+                sgn += homography::side(Q, fa, fb);
+        }
+    }
+    hom_reduce(sh, sgn, none, unused);  // its barriers also free hs.factor
+    if (!ok) return false;
+    if (sgn < 0) homography::negate(Q);
+    return true;
+}
+
+template <bool STAGED>
+__device__ __forceinline__ void homography_pair(const HomArgs& a, size_t pair, long long ob,
+                                                long long cnt, unsigned usable,
+                                                const double* __restrict__ rec, size_t stride,
+                                                RansacShared& sh, HomShared& hs) {
+    const double qnan = __builtin_nan("");
+    const int tid = threadIdx.x;
+    if (usable < 4u) return hom_fail(a, pair, ob, cnt, ACM_HOMOGRAPHY_TOO_FEW_MATCHES, 0u);
+    // the lane's best: count (-1: no model), score, hypothesis, model
+    int bc = -1, bh = 0;
+    double bsum = 0.0, bm[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) bm[k] = qnan;
+#pragma unroll 1
+    for (int h = tid; h < a.H; h += kBlock) {
+        HomSample s;
+        int got = 0;
+#pragma unroll 1
+        for (int d = 0; d < 8 && got < 4; ++d) {
+            const long long j = ransac::draw(a.seed, h, d, 8, cnt);
+            if (!__builtin_isfinite(rec[j]) || s.has(j)) continue;
+            s.set(got, j);
+            ++got;
+        }
+        if (got < 4) continue;
+        double H[9];
+        if (!homography::fit_rows(
+                4,
+                [=](long long i, double(&fa)[3], double(&fb)[3]) {
+                    const long long j = s.get((int)i);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        fa[k] = rec[k * stride + j];
+                        fb[k] = rec[(3 + k) * stride + j];
+                    }
+                    return true;
+                },
+                H))
+            continue;
+        int c = 0;
+        double sum = 0.0;
+        for (long long j = 0; j < cnt; ++j) {
+            const double ax = rec[j];
+            if (!__builtin_isfinite(ax)) continue;
+            double e;
+            if (homography::inlier(H, ax, rec[stride + j], rec[2 * stride + j], rec[3 * stride + j],
+                                   rec[4 * stride + j], rec[5 * stride + j], a.sin2, e)) {
+                ++c;
+                sum += e;
+            }
+        }
+        // h only grows in a lane: a tie keeps the earlier
+        if (c > bc || (c == bc && sum < bsum)) {
+            bc = c;
+            bsum = sum;
+            bh = h;
+#pragma unroll
+            for (int q = 0; q < 9; ++q) bm[q] = H[q];
+        }
+    }
+    const int winner = ransac_select<false>(sh, nullptr, ransac::Key{bc, bsum, bh, 0});
+    int best = sh.count[0];
+    double best_sum = sh.score[0];
+    if (best < a.min_inliers)  // also no model at all: best = -1
+        return hom_fail(a, pair, ob, cnt, ACM_HOMOGRAPHY_NO_MODEL, best < 0 ? 0u : (uint32_t)best);
+    if (tid == winner) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) hs.model[q] = bm[q];
+    }
+    __syncthreads();  // also: every lane has read sh.count[0] and sh.score[0]
+    double H[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) H[q] = hs.model[q];
+    // the refit: every condition below is the same in all lanes
+#pragma unroll 1
+    for (int round = 0; round < a.refit_rounds; ++round) {
+        double Q[9];
+        if (!hom_refit(H, rec, stride, cnt, a.sin2, sh, hs, Q)) break;
+        int c;
+        double sum;
+        hom_score(Q, rec, stride, cnt, a.sin2, sh, c, sum);
+        if (!(c > best || (c == best && sum < best_sum))) break;
+        best = c;
+        best_sum = sum;
+#pragma unroll
+        for (int q = 0; q < 9; ++q) H[q] = Q[q];
+    }
+    // the final model, decomposed once; cheirality over its inliers
+    double lam[3], V[9], tau;
+    homography::Motion A, B;
+    homography::spectrum(H, lam, V);
+    const int n_dec = homography::decompose(H, lam, V, A, B, tau);
+    homography::Front f;
+    if (n_dec == 2) {
+        for (long long j = tid; j < cnt; j += kBlock) {
+            const double fa[3] = {rec[j], rec[stride + j], rec[2 * stride + j]};
+            double e;
+            if (__builtin_isfinite(fa[0]) &&
+                homography::inlier(H, fa[0], fa[1], fa[2], rec[3 * stride + j], rec[4 * stride + j],
+                                   rec[5 * stride + j], a.sin2, e))
+                homography::front_add(A, B, fa, f);
+        }
+    }
+    hom_reduce(sh, f.pos0, f.neg0, f.sum0);
+    hom_reduce(sh, f.pos1, f.neg1, f.sum1);
+    double P[24], L[8];
+    unsigned front[2];
+    const int n_sol = homography::finish(n_dec, A, B, f, (long long)best, P, L, front);
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) a.hom[9 * pair + q] = H[q];
+        a.status[pair] = ACM_HOMOGRAPHY_OK;
+        a.n_inliers[pair] = (uint32_t)best;
+        if (a.poses) {
+            double* dst = reinterpret_cast<double*>(a.poses + 2 * pair);
+#pragma unroll
+            for (int q = 0; q < 24; ++q) dst[q] = P[q];
+        }
+        if (a.planes) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) a.planes[8 * pair + q] = L[q];
+        }
+        if (a.n_solutions) a.n_solutions[pair] = (uint8_t)n_sol;
+        if (a.n_front) {
+            a.n_front[2 * pair] = front[0];
+            a.n_front[2 * pair + 1] = front[1];
+        }
+        if (a.translation) a.translation[pair] = n_sol ? tau : qnan;
+    }
+    write_inlier_mask(a.mask, ob, cnt, rec, stride,
+                      [&](double ax, double ay, double az, double bx, double by, double bz) {
+                          double e;
+                          return homography::inlier(H, ax, ay, az, bx, by, bz, a.sin2, e);
+                      });
+}
+
+template <class TagT>
+__global__ __launch_bounds__(kBlock) void k_homography(CamArg cam, HomArgs a) {
+    __shared__ double s_rec[6 * kHomStage];  // planes fa.x, fa.y, fa.z, fb.x, fb.y, fb.z
+    __shared__ RansacShared sh;
+    __shared__ HomShared hs;
+    const Cam<double> c = make_cam<double>(cam);
+    const size_t pair = blockIdx.x;
+    long long ob, cnt;
+    clamped_range(a.offs, pair, a.n_matches, ob, cnt);
+    const bool staged = cnt <= (long long)kHomStage;  // workgroup-uniform
+    // the records: j < cnt <= n_matches - ob, so a workspace plane is never overrun
+    double* wrec = a.ws + ob;
+    const size_t wstride = a.n_matches;
+    const unsigned usable = stage_records<kHomStage>(
+        cnt, staged, s_rec, wrec, wstride, sh.usable, [&](long long j, double(&r)[6]) {
+            return pixel_bearing<TagT, true>(c, a.uv_a[2 * (ob + j)], a.uv_a[2 * (ob + j) + 1], r[0],
+                                             r[1], r[2]) &&
+                   pixel_bearing<TagT, true>(c, a.uv_b[2 * (ob + j)], a.uv_b[2 * (ob + j) + 1], r[3],
+                                             r[4], r[5]);
+        });
+    if (threadIdx.x == 0 && a.n_usable) a.n_usable[pair] = usable;
+    if (staged)
+        homography_pair<true>(a, pair, ob, cnt, usable, s_rec, (size_t)kHomStage, sh, hs);
+    else
+        homography_pair<false>(a, pair, ob, cnt, usable, wrec, wstride, sh, hs);
 }
 
 // ------------------------------------------------------------ calibration
@@ -7360,6 +7725,91 @@ ACM_API int acm_relative_pose_batch(const acm_camera* cam, size_t n_pairs, acm_p
         hipLaunchKernelGGL(k_relative_pose<TagT>, dim3((unsigned)n_pairs), dim3(kBlock), 0, s,
                            prep(*cam, false, true), a);
         return check_launch("acm_relative_pose_batch");
+    });
+}
+
+ACM_API int acm_homography_4pt(size_t n, const double* bearings_a, const double* bearings_b,
+                               double* homography, acm_pose* poses, double* planes,
+                               double* translation, uint8_t* count, uint8_t* n_front,
+                               void* stream) {
+    if (n == 0) return ACM_SUCCESS;
+    if (!bearings_a || !bearings_b || !homography || !poses || !planes || !count || !n_front)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (n > (size_t)0x7fffffff * kBlock)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many problems for one launch");
+    const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_homography_4pt, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, n,
+                       bearings_a, bearings_b, homography, poses, planes, translation, count,
+                       n_front);
+    return check_launch("acm_homography_4pt");
+}
+
+ACM_API void acm_homography_batch_default_config(acm_homography_config* cfg) {
+    if (!cfg) return;
+    cfg->n_hypotheses = 256;
+    cfg->flags = 0;
+    cfg->seed = 1;
+    cfg->inlier_angle = 5e-3;
+    cfg->min_inliers = 4;
+    cfg->refit_rounds = 3;
+}
+
+// 64 reserved bytes, then the records of the pairs too long for LDS: six
+// planes of n_matches doubles (a pair uses its own range of each plane)
+ACM_API size_t acm_homography_batch_workspace_size(size_t, size_t n_matches) {
+    return 64 + 48 * n_matches;
+}
+
+ACM_API int acm_homography_batch(const acm_camera* cam, size_t n_pairs,
+                                 const int64_t* pair_offsets, size_t n_matches,
+                                 const double* uv_a, const double* uv_b,
+                                 const acm_homography_config* cfg, double* homography,
+                                 uint8_t* status, uint32_t* n_inliers, acm_pose* poses,
+                                 double* planes, uint8_t* n_solutions, uint32_t* n_front,
+                                 double* translation, uint8_t* inlier_mask, uint32_t* n_usable,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_cam(cam);
+    if (rc) return rc;
+    if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
+    if (!ransac_config_ok(*cfg, 4) || cfg->refit_rounds < 0 || cfg->refit_rounds > 8)
+        return fail(ACM_ERR_INVALID_ARGUMENT,
+                    "n_hypotheses outside 1 .. 65536, nonzero flags, inlier_angle outside (0, pi/2), "
+                    "min_inliers < 4 or refit_rounds outside 0 .. 8");
+    if (n_pairs == 0) return ACM_SUCCESS;
+    if (!homography || !pair_offsets || !status || !n_inliers || (n_matches && (!uv_a || !uv_b)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace || workspace_bytes < acm_homography_batch_workspace_size(n_pairs, n_matches))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "homography workspace too small");
+    if (n_pairs > (size_t)0x7fffffff)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many pairs for one launch");
+    hipStream_t s = (hipStream_t)stream;
+    return dispatch_model(cam->model, [&](auto tag) -> int {
+        using TagT = decltype(tag);
+        HomArgs a;
+        a.n_matches = n_matches;
+        a.offs = pair_offsets;
+        a.uv_a = uv_a;
+        a.uv_b = uv_b;
+        a.hom = homography;
+        a.status = status;
+        a.n_inliers = n_inliers;
+        a.poses = poses;
+        a.planes = planes;
+        a.n_solutions = n_solutions;
+        a.n_front = n_front;
+        a.translation = translation;
+        a.mask = inlier_mask;
+        a.n_usable = n_usable;
+        a.ws = reinterpret_cast<double*>(static_cast<char*>(workspace) + 64);
+        a.H = cfg->n_hypotheses;
+        a.min_inliers = cfg->min_inliers;
+        a.refit_rounds = cfg->refit_rounds;
+        a.seed = cfg->seed;
+        const double si = std::sin(cfg->inlier_angle);
+        a.sin2 = si * si;
+        hipLaunchKernelGGL(k_homography<TagT>, dim3((unsigned)n_pairs), dim3(kBlock), 0, s,
+                           prep(*cam, false, true), a);
+        return check_launch("acm_homography_batch");
     });
 }
 

@@ -920,10 +920,12 @@ ACM_API int acm_pose_estimate_batch(const acm_camera *cam, size_t n_views, acm_p
  *
  * Out of scope: a 5-point minimal solver (it survives planar scenes and needs
  * 5 instead of 8 clean matches per sample, but its 10 x 20 elimination and
- * degree-10 root finding do not fit a lane's registers); detection of pure
- * rotation and planar scenes (acm_triangulate's ACM_TRI_DEGENERATE reports the
- * missing parallax downstream); a non-linear refinement of E; two different
- * cameras per pair; spreading one pair's hypotheses over several workgroups. */
+ * degree-10 root finding do not fit a lane's registers); pure rotation and
+ * planar scenes, whose model is the homography of acm_homography_4pt and
+ * acm_homography_batch below (their inlier count and tau beside this call's
+ * count are what a choice between the two models needs; the choice itself is
+ * the caller's); a non-linear refinement of E; two different cameras per
+ * pair; spreading one pair's hypotheses over several workgroups. */
 ACM_API int acm_relative_pose_8pt(size_t n, const double *bearings_a, const double *bearings_b,
                                   acm_pose *poses, double *essential, uint8_t *n_front,
                                   void *stream);
@@ -956,6 +958,141 @@ ACM_API int acm_relative_pose_batch(const acm_camera *cam, size_t n_pairs, acm_p
                                     uint32_t *n_inliers, uint8_t *inlier_mask,
                                     uint32_t *n_usable, void *workspace,
                                     size_t workspace_bytes, void *stream);
+
+/* Two-view homography: the 4-point solver and RANSAC over it.  When all
+ * matches lie on one plane, or camera B only rotates, the 8-point system above
+ * loses rank; the model of exactly those two cases is f_b ~ H f_a for the
+ * bearings of a match, H = R + (t / d) n^T with the plane n . X = d > 0 in
+ * camera A's frame (n a unit vector) and the motion p_b = R p_a + t.  Like the
+ * calls above these work on bearing vectors and serve all seven models.
+ *
+ * acm_homography_4pt: n independent problems of four matches, one lane each.
+ * bearings_a, bearings_b: 12 n f64, problem i holds its four bearings in image
+ * A and in image B (any length; the call normalises them).  Outputs per
+ * problem: homography, 9 f64, H row-major with its middle singular value 1 and
+ * f_b . (H f_a) > 0 for the majority of the four matches; count, one byte, the
+ * number of solutions 0, 1 or 2; poses, two acm_pose, the motion of each
+ * solution with t scaled to unit length (acm_relative_pose_*'s convention);
+ * planes, 2 x 4 f64, (n_x, n_y, n_z, d / |t|) of each solution; translation
+ * (nullable), one f64, tau = sigma_1 - sigma_3 = |t| / d, the baseline over the
+ * plane's distance; n_front, two bytes, per solution the number of the four
+ * matches with n . f_a > 0.  The slots beyond count are NaN (n_front 0).
+ *
+ * The route, f64 throughout, works for any match count >= 4 (the refit below
+ * reuses it).  Match i gives the three rows [f_b]x (x) f_a, so that the rows
+ * times vec(H) are f_b x (H f_a); all three are fed, because for an
+ * omnidirectional bearing no fixed one is redundant.  They go through the
+ * Givens factor R9 and the inverse-iteration null vector of
+ * acm_relative_pose_8pt.  The eigenpairs lambda_1 >= lambda_2 >= lambda_3, v_1,
+ * v_2, v_3 of the symmetric H^T H come from a cyclic Jacobi of six sweeps; H is
+ * divided by sqrt(lambda_2) and negated when f_b . (H f_a) < 0 for more rows
+ * than > 0.  H with lambda_3 <= 2^-40 lambda_1 is singular.  For exactly four
+ * matches, three bearings of one image within 2^-40 of a common plane through
+ * the centre (|det(f_i, f_j, f_k)| <= 2^-40: three collinear image points,
+ * repeated matches included) leave H undetermined and fail the solve.
+ *
+ * Decomposition (Ma, Soatto, Kosecka, Sastry, An Invitation to 3-D Vision,
+ * 5.3), with lambda_2 = 1: u+- = (sqrt(1 - lambda_3) v_1 +- sqrt(lambda_1 - 1)
+ * v_3) / sqrt(lambda_1 - lambda_3), U = [v_2, u, v_2 x u], W = [H v_2, H u,
+ * H v_2 x H u], R = W U^T (made a rotation by Gram-Schmidt as above), n = v_2 x
+ * u, t / d = (H - R) n: two (R, t / d, n).  For each, the sign of (t, n) is the
+ * one for which more rows have n . f_a > 0 (the point is in front of A on the
+ * plane), a tie takes the sign as computed, and n_front is that count.  The
+ * two are ordered by n_front descending, then by the sum of n . f_a over the
+ * rows descending; which of them is the scene's is not decidable from two
+ * views.  tau = (lambda_1 - lambda_3) / (sqrt(lambda_1) + sqrt(lambda_3)).
+ *
+ * The error of (t^, n) grows like eps / tau and calling the motion a rotation
+ * costs tau, so at tau <= 2^-24 the call returns count 1: R = H made a
+ * rotation, t = 0, the plane 0, n_front = the number of rows.  This guards a
+ * 0 / 0; with noise the caller reads tau.
+ *
+ * A non-finite input, a bearing without direction, a degenerate sample, a
+ * singular or non-finite H: every output NaN, count 0, n_front 0.  n = 0 is
+ * valid.  NULL buffers (translation excepted) with n > 0:
+ * ACM_ERR_INVALID_ARGUMENT.  No workspace, stream-ordered, reentrant.
+ *
+ * acm_homography_batch: RANSAC over that solver, one 256-lane workgroup per
+ * view pair, all pairs in one launch.  The matches (CSR by pair, clamped
+ * offsets), the usable-match rule and the bearings (UCM's inverse of the
+ * projection, RadTan polished), the records of 48 B in LDS for a pair of at
+ * most ACM_HOMOGRAPHY_STAGE_MATCHES matches and in the workspace beyond, and
+ * n_usable are acm_relative_pose_batch's.
+ *
+ * Hypothesis h = 0 .. n_hypotheses - 1 (lanes stride over h) draws local
+ * indices with the same splitmix64 and ctr = 8 h + d + 1 for the draws d = 0
+ * .. 7.  The first four draws that are usable and pairwise distinct form the
+ * sample; otherwise the hypothesis is void.  Its model is the normalised,
+ * signed H of the solver above (no decomposition), scored over all usable
+ * matches of the pair in order: with g = H f_a and c = f_b x g a match is an
+ * inlier iff f_b . g > 0 and c . c <= sin^2(inlier_angle) (g . g) -- f_b lies
+ * within inlier_angle of the transferred bearing.  The key of a hypothesis is
+ * (inlier count descending, sum over the inliers of c . c / g . g ascending, h
+ * ascending), a total order.
+ *
+ * Refit, as acm_relative_pose_batch's: up to refit_rounds times the rows of
+ * the current model's inliers are streamed into R9 (lane l the matches l, l +
+ * 256, ...; the fixed butterfly, then the four waves in order), the result
+ * normalised, signed by the majority over those inliers and scored; it
+ * replaces the model iff strictly better, otherwise the loop ends.  After the
+ * last round the final H is decomposed once as above, the cheirality counts
+ * and sums taken over the final inliers and added by a fixed tree.
+ *
+ * Outputs per pair: homography (9 f64, required), status
+ * (acm_homography_status, required), n_inliers (required) and, each nullable,
+ * poses (two acm_pose), planes (2 x 4 f64), n_solutions (one byte), n_front
+ * (two uint32), translation (tau), inlier_mask (one byte per match) and
+ * n_usable.  A final H whose decomposition is not finite keeps status OK with
+ * n_solutions 0 and NaN motions.  Fewer than 4 usable matches:
+ * ACM_HOMOGRAPHY_TOO_FEW_MATCHES.  No hypothesis with a model, or a best count
+ * below min_inliers (no refit then): ACM_HOMOGRAPHY_NO_MODEL with n_inliers =
+ * the best count (0 without a model).  In both cases n_inliers aside every
+ * f64 output is NaN, every count 0 and the pair's mask 0.
+ *
+ * A pair's outputs depend only on its own match list in order, the camera and
+ * the config, and repeated calls return the same bits.  Errors:
+ * acm_relative_pose_batch's list with min_inliers < 4 in place of < 8.
+ * n_pairs = 0 is valid and touches nothing.  Stream-ordered, no allocation,
+ * no host synchronisation, reentrant (two calls in flight need two
+ * workspaces).
+ *
+ * Out of scope: choosing between the essential matrix and the homography;
+ * picking one of the two plane solutions (a third view or a known normal
+ * does); a non-linear refinement of H; two different cameras per pair. */
+ACM_API int acm_homography_4pt(size_t n, const double *bearings_a, const double *bearings_b,
+                               double *homography, acm_pose *poses, double *planes,
+                               double *translation, uint8_t *count, uint8_t *n_front,
+                               void *stream);
+
+typedef enum acm_homography_status {
+    ACM_HOMOGRAPHY_OK = 0,
+    ACM_HOMOGRAPHY_TOO_FEW_MATCHES = 1, /* fewer than 4 usable matches */
+    ACM_HOMOGRAPHY_NO_MODEL = 2         /* no finite model, or fewer than min_inliers inliers */
+} acm_homography_status;
+
+/* matches of one pair whose records stay in LDS (48 B each); a longer pair
+ * keeps them in the workspace */
+#define ACM_HOMOGRAPHY_STAGE_MATCHES 1024
+
+typedef struct acm_homography_config {
+    int32_t n_hypotheses;   /* default 256; 1 .. 65536 */
+    int32_t flags;          /* must be 0 */
+    uint64_t seed;          /* default 1 */
+    double inlier_angle;    /* radians, in (0, pi/2); default 5e-3 */
+    int32_t min_inliers;    /* default 4; >= 4 */
+    int32_t refit_rounds;   /* default 3; 0 .. 8 */
+} acm_homography_config;
+
+ACM_API void acm_homography_batch_default_config(acm_homography_config *cfg);
+ACM_API size_t acm_homography_batch_workspace_size(size_t n_pairs, size_t n_matches);
+ACM_API int acm_homography_batch(const acm_camera *cam, size_t n_pairs,
+                                 const int64_t *pair_offsets, size_t n_matches,
+                                 const double *uv_a, const double *uv_b,
+                                 const acm_homography_config *cfg, double *homography,
+                                 uint8_t *status, uint32_t *n_inliers, acm_pose *poses,
+                                 double *planes, uint8_t *n_solutions, uint32_t *n_front,
+                                 double *translation, uint8_t *inlier_mask, uint32_t *n_usable,
+                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /* Multi-view calibration: the intrinsics and every view's pose in one
  * Levenberg-Marquardt.  K views of known world points, rough poses (device,
