@@ -25,6 +25,11 @@ Families (sample parameters of samples/*.yaml unless noted):
   Pinhole / RadTan project  z = sqrt(EPS), u = w and v = h bounds
   RadTan unproject          a near-singular Newton Jacobian (k1 = -1/3:
                             det ~ 1e-16 at the first step)
+  alpha <= 0.5 (tests/camera_zoo.py's *_alpha_lt_half and *_alpha_half):
+  UCM / DS / EUCM project   denom = 1e-3, and z vs -w d with w = a / (1 - a)
+                            (UCM, DS), also at |p| ~ 1e13
+  UCM unproject             1 - r^2 = 1e-3 (_alpha_le_half_probes says why
+                            DS and EUCM have no reachable threshold there)
 """
 import mpmath
 import numpy as np
@@ -123,11 +128,6 @@ def probes():
     pts += [[x, 0.0, 2.0] for x in _ulps(-cx / fx * 2.0)]
     out.append((0, S_PIN, (752, 480), "project", np.array(pts)))
     # ---- unprojections: pixel u along the x axis (v = cy)
-    def pix(p, mx_target_sq, scale):
-        """pixels u = cx + fx * m with (m * scale)^2 at the root"""
-        m0 = mp.sqrt(mp.mpf(mx_target_sq)) / scale
-        u0 = mp.mpf(p[2]) + mp.mpf(p[0]) * m0
-        return [[u, p[3]] for u in _ulps(u0)]
     a = mp.mpf(S_DS[4])
     out.append((3, S_DS, (0, 0), "unproject", np.array(pix(S_DS, 1 / (2 * a - 1), 1))))
     a = mp.mpf(S_UCM[4])
@@ -148,7 +148,90 @@ def probes():
     pts = [[cx + fx * m, cy + fy * n] for m in (1.0, 0.999999, 1.000001, 0.5, 0.99)
            for n in (0.0, 1e-9, -1e-6, 1e-3)]
     out.append((1, S_RT_SING, (2000, 2000), "unproject", np.array(pts)))
+    return out + _alpha_le_half_probes()
+
+
+def _alpha_le_half_probes():
+    """The families that exist only for alpha <= 0.5 (tests/camera_zoo.py's
+    *_alpha_lt_half and *_alpha_half cameras).
+
+    There w = alpha / (1 - alpha) (ucm.rs:154-161, double_sphere.rs:177-184).
+    Each family holds (a) denom = 1e-3 at three radii, one of them large
+    enough that a d and (1 - a) z cancel, (b) the root of z = -w d (DS: -w2
+    d1) at the scale of the sample families, and (c) the same root at |p| ~
+    1e13, where one ulp of a d is about 1e-3 and the rounded denom passes 1e-3
+    for part of the +-8 ulp window.  For UCM z = -w d is the zero of denom
+    itself, so denom >= 1e-3 implies the condition; that held on every probe
+    tried up to |p| = 1e18, i.e. UCM's condition is redundant for alpha <= 0.5
+    and a wrong w there cannot show in a status.  DS's condition is not
+    implied: a build with DS's two arms of w1 swapped differs from the oracle
+    on the denom probes at r = 0.3 here.  EUCM's condition is constant true
+    for alpha <= 0.5: denom = 1e-3 only.
+
+    Unprojection: UCM's 1 - r^2 = 1e-3 is the one threshold a pixel can reach
+    (its alpha > 0.5 condition is gone).  EUCM's det = 1 - (2a - 1) b r^2 is
+    >= 1, and DS's denom = mz^2 + r^2 is >= 1 for every r^2 >= 0 (it is 1 at
+    r^2 = 0 with slope 1 - alpha > 0 and no interior minimum), so neither has
+    a reachable threshold for alpha <= 0.5.
+    """
+    from camera_zoo import camera_of
+    mp = mpmath
+    out = []
+    thr = mp.mpf("1e-3")
+    for name in ("ucm_alpha_lt_half", "ucm_alpha_half"):
+        model, p, res = camera_of(name)
+        a = mp.mpf(p[4])
+        w = a / (1 - a)
+        pts = []
+        for r, z_start in ((1e-4, 1e-3), (6e-4, 1e-3), (0.3, -0.2 if a < 0.5 else -40.0)):
+            z0 = _root(lambda z, r=r: a * mp.sqrt(2 * r * r + z * z) + (1 - a) * z - thr, z_start)
+            pts += [[r, r, z] for z in _ulps(z0)]
+        for r in (0.1, 0.4, 1e13, 3e13):
+            # z = -w d  <=>  z = -w r sqrt(2) / sqrt(1 - w^2); at w = 1 (alpha =
+            # 0.5) the root is at z = -inf: take d + z ~ 2e-3 r^2 / |z| instead
+            with mp.workdps(60):
+                zc = -w * r * mp.sqrt(2) / mp.sqrt(1 - w * w) if a < 0.5 else -mp.mpf(r) * 1e3
+            pts += [[r, r, z] for z in _ulps(zc)]
+        out.append((model, p, res, "project", np.array(pts)))
+        g = 1 - a
+        out.append((model, p, (0, 0), "unproject", np.array(pix(p, mp.mpf("0.999"), abs(g)))))
+    for name in ("ds_alpha_lt_half", "ds_alpha_half"):
+        model, p, res = camera_of(name)
+        a, xi = mp.mpf(p[4]), mp.mpf(p[5])
+        w1 = a / (1 - a)
+        w2 = (w1 + xi) / mp.sqrt(2 * w1 * xi + xi * xi + 1)
+
+        def den(z, r):
+            d1 = mp.sqrt(2 * r * r + z * z)
+            g = xi * d1 + z
+            return a * mp.sqrt(2 * r * r + g * g) + (1 - a) * g
+        pts = []
+        for r, z_start in ((1e-4, 1e-3), (4e-4, 1e-3), (0.3, -0.3)):
+            z0 = _root(lambda z, r=r: den(z, r) - thr, z_start)
+            pts += [[r, r, z] for z in _ulps(z0)]
+        for r in (0.1, 0.4, 1e13, 3e13):
+            with mp.workdps(60):
+                zc = -w2 * r * mp.sqrt(2) / mp.sqrt(1 - w2 * w2) if w2 < 0.999 else -mp.mpf(r) * 1e3
+            pts += [[r, r, z] for z in _ulps(zc)]
+        out.append((model, p, res, "project", np.array(pts)))
+    for name in ("eucm_alpha_lt_half", "eucm_alpha_half"):
+        model, p, res = camera_of(name)
+        a, b = mp.mpf(p[4]), mp.mpf(p[5])
+        pts = []
+        for r, z_start in ((1e-4, 1e-3), (5e-4, 1e-3), (0.3, -0.3 if a < 0.5 else -40.0)):
+            z0 = _root(lambda z, r=r: a * mp.sqrt(b * 2 * r * r + z * z) + (1 - a) * z - thr,
+                       z_start)
+            pts += [[r, r, z] for z in _ulps(z0)]
+        out.append((model, p, res, "project", np.array(pts)))
     return out
+
+
+def pix(p, mx_target_sq, scale):
+    """pixels u = cx + fx * m along the x axis (v = cy) with (m * scale)^2 at
+    the root, +-8 ulps"""
+    m0 = mpmath.sqrt(mpmath.mpf(mx_target_sq)) / scale
+    u0 = mpmath.mpf(p[2]) + mpmath.mpf(p[0]) * m0
+    return [[u, p[3]] for u in _ulps(u0)]
 
 
 # ----------------------------------------------------------- f64 emulation

@@ -3,8 +3,9 @@
 Scene: the K = 6 poses of triangulation_ref.rig("wide").  View k observes its
 own block of 100 world points: the pixels of a 10 x 10 grid
   u = (0.1 + 0.8 (jx + 0.5 + 0.03 k) / 10) w,  v = (0.1 + 0.8 (jy + 0.5 + 0.03 k) / 10) h
-(j = 10 jy + jx) unprojected by the oracle with the samples.SAMPLES
-intrinsics, each unit ray scaled to the distance 1.5 + 2.5 frac(0.6180339887 j
+(j = 10 jy + jx) unprojected by the oracle with the intrinsics of camera `mid`
+(camera_zoo.camera_of: a model id for its sample camera, or a zoo name), each
+unit ray scaled to the distance 1.5 + 2.5 frac(0.6180339887 j
 + 0.1 k) and moved to the world by the inverse true pose.  The observed pixel
 is the oracle's re-projection (+ N(0, noise) pixels, seed 20251207).
 
@@ -24,7 +25,7 @@ import numpy as np
 
 import oracle
 import triangulation_ref as T
-from apex_camera_models import samples
+from camera_zoo import camera_of
 
 K_VIEWS = T.K_VIEWS
 N_SIDE = 10
@@ -56,7 +57,7 @@ def start_poses():
 
 
 def true_params(mid):
-    return np.array(samples.SAMPLES[mid][0], dtype=np.float64)
+    return np.array(camera_of(mid)[1], dtype=np.float64)
 
 
 def start_params(mid):
@@ -74,17 +75,17 @@ def scene(mid):
     """(world (600, 3), offsets (7,) int64, obs_point (600,) int32, uv (600, 2),
     n_ok): view k's block is rows 100 k .. 100 k + 99; n_ok counts the grid
     pixels that unprojected and re-projected Ok on the oracle."""
-    params, (w, h) = samples.SAMPLES[mid]
+    model, params, (w, h) = camera_of(mid)
     poses = true_poses()
     world, uvs, n_ok = [], [], 0
     j = np.arange(N_PER_VIEW)
     for k in range(K_VIEWS):
         f = 0.1 + 0.8 * (np.stack([j % N_SIDE, j // N_SIDE], axis=1) + 0.5 + 0.03 * k) / N_SIDE
         px = f * [w, h]
-        rays, st = oracle.unproject(mid, params, w, h, px)
+        rays, st = oracle.unproject(model, params, w, h, px)
         depth = 1.5 + 2.5 * np.mod(0.6180339887 * j + 0.1 * k, 1.0)
         p = rays * depth[:, None]
-        uv, st2, _ = oracle.project(mid, params, w, h, p)
+        uv, st2, _ = oracle.project(model, params, w, h, p)
         n_ok += int(((st == 0) & (st2 == 0)).sum())
         R, t = poses[k, :9].reshape(3, 3), poses[k, 9:]
         world.append((p - t) @ R)  # R^T (p - t), row vectors
@@ -108,7 +109,7 @@ def observed(mid, noise_px=0.0):
 
 def residuals(mid, theta, poses, uv):
     """((600, 2) residuals with invalid rows 0, n_valid) on the oracle."""
-    _, (w, h) = samples.SAMPLES[mid]
+    model, _, (w, h) = camera_of(mid)
     world = scene(mid)[0]
     r = np.zeros((len(world), 2))
     nv = 0
@@ -116,7 +117,7 @@ def residuals(mid, theta, poses, uv):
         sl = slice(N_PER_VIEW * k, N_PER_VIEW * (k + 1))
         R, t = poses[k, :9].reshape(3, 3), poses[k, 9:]
         with np.errstate(all="ignore"):
-            p, st, _ = oracle.project(mid, list(theta), w, h, world[sl] @ R.T + t)
+            p, st, _ = oracle.project(model, list(theta), w, h, world[sl] @ R.T + t)
             d = p - uv[sl]
         ok = (st == 0) & np.isfinite(d).all(axis=1)
         d[~ok] = 0.0

@@ -1,6 +1,9 @@
 """Reference data for the point-Jacobian and pose tests (not a test).
 
-Base set (250 points per model, from samples.SAMPLES[model]): a 12 x 10
+Every function takes a camera key (camera_zoo.camera_of): a model id for the
+sample camera of samples.SAMPLES, or the name of a zoo camera.
+
+Base set (250 points per camera): a 12 x 10
 pixel grid u = w (0.1 + 0.8 (j + 0.5) / 12), v = h (0.1 + 0.8 (i + 0.5) / 10)
 unprojected with the CPU oracle, each ray scaled by 0.7 and by 2.5 (240
 points), then (0, 0, 1.5) and (1e-7, -2e-7, 1.0) (on / near the axis), then
@@ -20,6 +23,7 @@ import numpy as np
 
 import mp_models
 import oracle
+from camera_zoo import camera_of
 from apex_camera_models import samples
 
 N_GRID = 240
@@ -31,9 +35,9 @@ EDGE_ROWS = (0, 1, 2, 16, 26, 27, 28, 29)
 
 
 @functools.lru_cache(maxsize=None)
-def base_points(model):
+def base_points(key):
     """(250, 3) float64 (read-only)."""
-    params, (w, h) = samples.SAMPLES[model]
+    model, params, (w, h) = camera_of(key)
     jj, ii = np.meshgrid(np.arange(12), np.arange(10))
     u = w * (0.1 + 0.8 * (jj.ravel() + 0.5) / 12)
     v = h * (0.1 + 0.8 * (ii.ravel() + 0.5) / 10)
@@ -64,17 +68,17 @@ def mp_point_jacobian(model, params, pt):
     return J
 
 
-def reference_rows(model, pts):
+def reference_rows(key, pts):
     """Which rows of pts get a reference: finite input and Ok on the oracle."""
-    params, (w, h) = samples.SAMPLES[model]
+    model, params, (w, h) = camera_of(key)
     _, st, _ = oracle.project(model, params, w, h, pts)
     return (st == 0) & np.isfinite(pts).all(axis=1)
 
 
-def mp_jacobians(model, pts):
+def mp_jacobians(key, pts):
     """(len(pts), 2, 3) float64, NaN rows where reference_rows is False."""
-    params, _ = samples.SAMPLES[model]
-    have = reference_rows(model, pts)
+    model, params, _ = camera_of(key)
+    have = reference_rows(key, pts)
     J = np.full((len(pts), 2, 3), np.nan)
     for i in np.nonzero(have)[0]:
         J[i] = mp_point_jacobian(model, params, pts[i])
@@ -83,14 +87,14 @@ def mp_jacobians(model, pts):
 
 
 @functools.lru_cache(maxsize=None)
-def base_jacobians(model):
-    """mp_jacobians of base_points(model) (read-only, cached)."""
-    return mp_jacobians(model, base_points(model))
+def base_jacobians(key):
+    """mp_jacobians of base_points(key) (read-only, cached)."""
+    return mp_jacobians(key, base_points(key))
 
 
-def mp_project(model, pts, rows):
+def mp_project(key, pts, rows):
     """(len(pts), 2) float64 50-digit projections of the rows in `rows` (NaN elsewhere)."""
-    params, _ = samples.SAMPLES[model]
+    model, params, _ = camera_of(key)
     uv = np.full((len(pts), 2), np.nan)
     for i in np.nonzero(rows)[0]:
         u, v = mp_models.project(model, params, pts[i])

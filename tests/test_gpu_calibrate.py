@@ -1,6 +1,8 @@
 """acm_calibrate on the GPU: the intrinsics and every view's pose in one LM.
 
-Sums (max_iterations = 0): the views are built as tests/test_gpu_pose_batch.py
+Sums (max_iterations = 0), all seven models at their sample cameras and the
+solver subset of tests/camera_zoo.py (views of 2, 257 and 1000 observations
+there): the views are built as tests/test_gpu_pose_batch.py
 builds them (point_jacobian_ref's 250-point base set with its NaN / Inf /
 behind-the-camera rows, noisy pixels, spoiled pixels and indices), all views
 over one block of world points and one start pose so that one 50-digit
@@ -16,7 +18,9 @@ scipy + 1e-9) and the pose bound of the fixed-intrinsics test (1e-6) are
 test_gpu_pose_batch.py's.
 
 Measured on an MI355X: sums, worst |gpu - exact| /
-bound KB 2.1e-3, DS 1.1e-3.  Zero noise: intrinsics error at most 5.8e-6 (KB;
+bound Pinhole 1.0e-3, RadTan 1.0e-3, KB 2.1e-3, DS 1.1e-3, UCM 3.3e-3, EUCM
+2.7e-3, FOV 3.1e-3; zoo cameras 3.0e-5 (pinhole_aniso) ... 7.5e-3
+(eucm_alpha_half).  Zero noise: intrinsics error at most 5.8e-6 (KB;
 RadTan 3.7e-6, the others <= 1.4e-8), pose errors <= 6.4e-9, 4-13 iterations,
 all as the numpy restatement.  Noise: cost / scipy <= 1 + 4.7e-9.  Bounded
 DoubleSphere: alpha on its bound, cost equal to bounded scipy's to 10 digits.
@@ -30,11 +34,11 @@ import pytest
 import torch
 
 import calibration_ref as C
+import camera_zoo as Z
 import mp_models
 import point_jacobian_ref as R
 import test_gpu_pose_batch as PB
-from apex_camera_models import Resolution, _lib, samples
-from apex_camera_models.camera import MODEL_CLASSES
+from apex_camera_models import _lib, samples
 from apex_camera_models.optimizer import (CalibrationConfig, CalibrationResult, calibrate,
                                           tracks_by_view)
 
@@ -48,9 +52,8 @@ TOLERANCE_STOPS = (1, 2, 3)  # ACM_LM_COST, ACM_LM_PARAMETER, ACM_LM_GRADIENT
 
 
 def _model(mid, params=None):
-    p, (w, h) = samples.SAMPLES[mid]
-    return MODEL_CLASSES[samples.MODEL_NAMES[mid]]._from_params(
-        list(p if params is None else params), Resolution(w, h))
+    """mid: a model id (its sample camera) or a zoo camera's name, here and below"""
+    return Z.device_model(mid, params)
 
 
 def _run(mid, params, poses, world, offsets, point, uv, max_iterations=None, fixed_mask=0,
@@ -77,7 +80,7 @@ def _run(mid, params, poses, world, offsets, point, uv, max_iterations=None, fix
     cost = torch.full((k,), -1.0, dtype=torch.float64, device=dev)
     n_valid = torch.full((k,), -1, dtype=torch.int32, device=dev)
     system = torch.full((k, 16, 16), -1.0, dtype=torch.float64, device=dev)
-    ws_bytes = L.acm_calibrate_workspace_size(mid, k, m)
+    ws_bytes = L.acm_calibrate_workspace_size(Z.camera_of(mid)[0], k, m)
     ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device=dev)
     cam = _model(mid, params).acm_camera()
     summ = _lib.CalibrateSummary()
@@ -105,7 +108,7 @@ def _sums_reference(mid):
     augmented rows M (250, 2, 16) without the residual, the 50-digit
     projections (250, 2) and the rows that have a reference."""
     J6, uv, have = PB._view_reference(mid, 0, 1)
-    params, _ = samples.SAMPLES[mid]
+    model, params, _ = Z.camera_of(mid)
     Rm, t = PB._Rt(PB._start_pose(0))
     with np.errstate(invalid="ignore"):
         p = PB._world(mid, 1) @ Rm.T + t
@@ -113,21 +116,21 @@ def _sums_reference(mid):
     M = np.zeros((N_BASE, 2, 16))
     M[:, :, :6] = np.where(have[:, None, None], J6, 0.0)
     for i in np.nonzero(have)[0]:
-        Ju, Jv = mp_models.jacobian(mid, list(params), p[i])
+        Ju, Jv = mp_models.jacobian(model, list(params), p[i])
         M[i, 0, 6:6 + P] = [float(v) for v in Ju]
         M[i, 1, 6:6 + P] = [float(v) for v in Jv]
     M.setflags(write=False)
     return M, uv, have
 
 
-def _sums_csr(mid):
-    """View k observes COUNTS[k] points of the one block, tiled from 17 k."""
-    K = len(COUNTS)
+def _sums_csr(mid, counts):
+    """View k observes counts[k] points of the one block, tiled from 17 k."""
+    K = len(counts)
     offsets = np.zeros(K + 1, dtype=np.int64)
-    offsets[1:] = np.cumsum(COUNTS)
+    offsets[1:] = np.cumsum(counts)
     m = int(offsets[-1])
     point = np.empty(m, dtype=np.int32)
-    for k, c in enumerate(COUNTS):
+    for k, c in enumerate(counts):
         point[offsets[k]:offsets[k + 1]] = (np.arange(c) + 17 * k) % N_BASE
     uv = PB._true_pixels(mid, 1)[point] + PB._noise()[:m]
     j = np.arange(m)
@@ -138,11 +141,12 @@ def _sums_csr(mid):
     return offsets, point, uv
 
 
-@pytest.mark.parametrize("mid", [KB, DS])
+@pytest.mark.parametrize("mid", tuple(MODELS) + Z.SOLVER_SUBSET)
 def test_sums_against_50_digits(mid):
-    K = len(COUNTS)
+    counts = COUNTS if mid in MODELS else PB.ZOO_COUNTS
+    K = len(counts)
     world = PB._world(mid, 1)
-    offsets, point, uv = _sums_csr(mid)
+    offsets, point, uv = _sums_csr(mid, counts)
     start = np.stack([PB._row(PB._start_pose(0))] * K)
     params = C.true_params(mid)
     P = len(params)
@@ -152,6 +156,7 @@ def test_sums_against_50_digits(mid):
     assert got["iterations"] == 0 and got["evaluations"] == 1
     assert not np.isfinite(world).all(), "the base set should carry NaN / Inf world points"
     M, uvb, have = _sums_reference(mid)
+    assert int(have.sum()) >= 240, "more than 10 base rows without a reference"
     worst, seen, used, total_cost, total_valid = 0.0, set(), 0, [], 0
     for k in range(K):
         sl = slice(offsets[k], offsets[k + 1])
@@ -161,7 +166,7 @@ def test_sums_against_50_digits(mid):
         valid = in_range & have[local] & np.isfinite(obs).all(axis=1) & \
             np.isfinite(world[local]).all(axis=1)
         nv = int(valid.sum())
-        assert got["n_valid"][k] == nv, (k, COUNTS[k], got["n_valid"][k], nv)
+        assert got["n_valid"][k] == nv, (k, counts[k], got["n_valid"][k], nv)
         S = got["system"][k]
         assert S.tobytes() == S.T.copy().tobytes(), (k, "the system is not symmetric")
         assert (S[6 + P:15, :] == 0.0).all() and (S[:, 6 + P:15] == 0.0).all(), (k, "padding")
@@ -169,11 +174,11 @@ def test_sums_against_50_digits(mid):
         rows[:, :, 15] = (uvb[local] - obs)[valid]
         flat = rows.reshape(-1, 16)
         if nv < 3:
-            assert got["status"][k] == _lib.POSE_TOO_FEW_OBSERVATIONS, (k, COUNTS[k])
+            assert got["status"][k] == _lib.POSE_TOO_FEW_OBSERVATIONS, (k, counts[k])
             assert math.isnan(got["cost"][k])
             seen.add("few")
         else:
-            assert got["status"][k] == _lib.POSE_OK, (k, COUNTS[k], got["status"][k])
+            assert got["status"][k] == _lib.POSE_OK, (k, counts[k], got["status"][k])
             seen.add("ok")
             used += 1
             total_valid += nv
@@ -185,7 +190,7 @@ def test_sums_against_50_digits(mid):
                 bound = max(1e-10 * abs(want), 1e-13 * mag)
                 if err > 0.0:
                     worst = max(worst, err / bound if bound > 0 else math.inf)
-                assert err <= bound, (k, COUNTS[k], a, b, S[a, b], want, err / max(bound, 1e-300))
+                assert err <= bound, (k, counts[k], a, b, S[a, b], want, err / max(bound, 1e-300))
         if nv >= 3:
             assert got["cost"][k] == 0.5 * S[15, 15]
             total_cost.append(got["cost"][k])
@@ -193,7 +198,7 @@ def test_sums_against_50_digits(mid):
     assert got["n_views_used"] == used and got["total_valid"] == total_valid
     assert abs(got["initial_cost"] - math.fsum(total_cost)) <= 1e-12 * got["initial_cost"]
     assert got["final_cost"] == got["initial_cost"]
-    print(f"calibrate sums {samples.MODEL_NAMES[mid]}: worst |gpu - exact| / bound = {worst:.3e}")
+    print(f"calibrate sums {Z.label(mid)}: worst |gpu - exact| / bound = {worst:.3e}")
 
 
 # ----------------------------------------------------------------- solver

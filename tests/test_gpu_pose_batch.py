@@ -5,13 +5,17 @@ tests/test_gpu_pose.py builds its own: the world points of a view are the base
 set moved by the inverse of that view's true pose, so the set's edge rows
 (behind the camera, NaN, Inf) are in every view.
 
-Sums (max_iterations = 0): per view the 21 + 6 + 1 sums against float64 terms
+Sums (max_iterations = 0), all seven models at their sample cameras and the
+solver subset of tests/camera_zoo.py (views of 2, 257 and 1000 observations
+there): per view the 21 + 6 + 1 sums against float64 terms
 from the 50-digit point Jacobians, summed with math.fsum, per entry |gpu -
 exact| <= max(1e-10 |exact|, 1e-13 sum |terms|) (test_pose_normal_equations'
 bound).  Solver: the bounds of tests/test_gpu_pose.py.
 
 Measured on an MI355X: sums, worst |gpu - exact| /
-bound KB 1.2e-3, DS 3.9e-4.  Zero noise (bound 1e-6): KB rotation error
+bound Pinhole 2.0e-4, RadTan 5.3e-4, KB 1.2e-3, DS 3.9e-4, UCM 2.9e-4, EUCM
+1.0e-3, FOV 2.0e-4; zoo cameras 3.1e-6 (pinhole_aniso) ... 9.1e-4
+(eucm_alpha_half).  Zero noise (bound 1e-6): KB rotation error
 4.9e-11 rad, translation error 2.6e-9 after 43-46 iterations; the other six
 models <= 1.0e-10 after 4-5.  Noise: cost / scipy <= 1 + 1.7e-8; largest
 relative difference to acm_pose_optimize's cost KB 5.0e-15, DS 6.6e-15.
@@ -24,11 +28,11 @@ import numpy as np
 import pytest
 import torch
 
+import camera_zoo as Z
 import oracle
 import point_jacobian_ref as R
 import triangulation_ref as T
-from apex_camera_models import Resolution, _lib, samples
-from apex_camera_models.camera import MODEL_CLASSES
+from apex_camera_models import _lib, samples
 from apex_camera_models.optimizer import (Pose, PoseBatchConfig, alternate_bundle_adjustment,
                                           refine_poses)
 
@@ -39,6 +43,8 @@ TRUE_DELTA = np.array([0.3, -0.1, 0.2, 0.1, -0.2, 0.15])
 START_DELTA = [0.02, -0.01, 0.015, 0.01, 0.02, -0.015]
 # the lane, wave, workgroup and staging boundaries
 COUNTS = (0, 1, 2, 3, 4, 63, 64, 65, 255, 256, 257, 1000, 1024, 1025, 3000)
+ZOO_COUNTS = (2, 257, 1000)  # too few to take part; across a wave and a workgroup seam
+ALL_MODELS = tuple(sorted(samples.SAMPLES))
 N_BASE = R.N_BASE
 # The solver bounds below are tests/test_gpu_pose.py's, which runs
 # acm_pose_optimize under acm_lm_default_config: 100 iterations.  The batched
@@ -50,8 +56,8 @@ LM_ITERATIONS = 100
 
 
 def _model(mid):
-    params, (w, h) = samples.SAMPLES[mid]
-    return MODEL_CLASSES[samples.MODEL_NAMES[mid]]._from_params(list(params), Resolution(w, h))
+    """mid: a model id (its sample camera) or a zoo camera's name, here and below"""
+    return Z.device_model(mid)
 
 
 def _Rt(pose):
@@ -188,11 +194,12 @@ def _view_reference(mid, k, n_views):
     return J6, uv, have
 
 
-@pytest.mark.parametrize("mid", [KB, DS])
+@pytest.mark.parametrize("mid", ALL_MODELS + Z.SOLVER_SUBSET)
 def test_sums_against_50_digits(mid):
-    K = len(COUNTS)
+    counts = COUNTS if mid in ALL_MODELS else ZOO_COUNTS
+    K = len(counts)
     world = _world(mid, K)
-    offsets, point, uv = _csr(mid, COUNTS, noisy=True, spoil=True)
+    offsets, point, uv = _csr(mid, counts, noisy=True, spoil=True)
     start = np.stack([_row(_start_pose(k)) for k in range(K)])
     got = _run(mid, start, world, offsets, point, uv, max_iterations=0)
     assert got["poses"].tobytes() == start.tobytes(), "max_iterations = 0 moved a pose"
@@ -205,21 +212,22 @@ def test_sums_against_50_digits(mid):
         local = np.where(in_range, idx - N_BASE * k, 0)
         assert ((local >= 0) & (local < N_BASE)).all()
         # only the points a view names need a reference
-        if COUNTS[k] == 0:
+        if counts[k] == 0:
             valid = np.zeros(0, dtype=bool)
         else:
             J6b, uvb, haveb = _view_reference(mid, k, K)
+            assert int(haveb.sum()) >= 240, "more than 10 base rows without a reference"
             valid = in_range & haveb[local] & np.isfinite(obs).all(axis=1) & \
                 np.isfinite(world[np.where(in_range, idx, 0)]).all(axis=1)
         nv = int(valid.sum())
-        assert got["n_valid"][k] == nv, (k, COUNTS[k], got["n_valid"][k], nv)
+        assert got["n_valid"][k] == nv, (k, counts[k], got["n_valid"][k], nv)
         assert got["iterations"][k] == 0
         if nv < 3:
-            assert got["status"][k] == _lib.POSE_TOO_FEW_OBSERVATIONS, (k, COUNTS[k])
+            assert got["status"][k] == _lib.POSE_TOO_FEW_OBSERVATIONS, (k, counts[k])
             assert math.isnan(got["cost"][k]) and (got["information"][k] == 0.0).all()
             seen.add("few")
             continue
-        assert got["status"][k] == _lib.POSE_OK, (k, COUNTS[k], got["status"][k])
+        assert got["status"][k] == _lib.POSE_OK, (k, counts[k], got["status"][k])
         seen.add("ok")
         J = J6b[local][valid]                 # (m, 2, 6)
         r = (uvb[local] - obs)[valid]         # (m, 2)
@@ -239,9 +247,9 @@ def test_sums_against_50_digits(mid):
         with np.errstate(divide="ignore", invalid="ignore"):
             ratio = np.where(err == 0, 0.0, err / bound)
         worst = max(worst, float(ratio.max()))
-        assert (err <= bound).all(), (k, COUNTS[k], int(np.argmax(ratio)), float(ratio.max()))
+        assert (err <= bound).all(), (k, counts[k], int(np.argmax(ratio)), float(ratio.max()))
     assert seen == {"few", "ok"}
-    print(f"pose batch sums {samples.MODEL_NAMES[mid]}: worst |gpu - exact| / bound = {worst:.3e}")
+    print(f"pose batch sums {Z.label(mid)}: worst |gpu - exact| / bound = {worst:.3e}")
 
 
 def _same(a, b, k_a, k_b, what):

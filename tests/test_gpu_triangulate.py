@@ -3,14 +3,21 @@
 References (tests/triangulation_ref.py): the numpy midpoint from oracle rays,
 scipy's TRF on oracle residuals, and 50-digit point Jacobians / projections
 (tests/point_jacobian_ref.py) for information and cost.  Every test asserts
-its input condition on the CPU before calling the GPU.
+its input condition on the CPU before calling the GPU.  The midpoint start and
+the information / cost sums run for all seven models at their sample cameras
+(each on triangulation_ref.rig_kind's rig: Pinhole and RadTan reject pixels
+outside the image and take the medium rig); the sums also run, at a given
+start with max_iterations = 0, on the solver subset of tests/camera_zoo.py.
 
-Measured on an MI355X: start vs numpy midpoint, worst error / bound KB
-3.9e-6, DS 2.6e-6 (cond(A) <= 445); zero noise from the displaced start
-(bound 1e-6): Pinhole 4.4e-9, RadTan 3.4e-8, KB 3.7e-8, DS 3.3e-8, UCM
+Measured on an MI355X: start vs numpy midpoint, worst error / bound Pinhole
+2.4e-6, RadTan 5.3e-6 (medium rig, cond(A) <= 645), KB 3.9e-6, DS 2.6e-6, UCM
+2.3e-6, EUCM 2.3e-6, FOV 5.0e-6 (cond(A) <= 445); zero noise from the
+displaced start (bound 1e-6): Pinhole 4.4e-9, RadTan 3.4e-8, KB 3.7e-8, DS 3.3e-8, UCM
 3.7e-9, EUCM 3.6e-8, FOV 3.9e-8; noisy cost / scipy cost KB 1 + 1.8e-10, DS
-1 + 1.1e-10; information and cost, worst |gpu - exact| / bound KB 1.3e-2,
-DS 3.8e-2.
+1 + 1.1e-10; information and cost, worst |gpu - exact| / bound Pinhole
+5.0e-3, RadTan 1.4e-2, KB 1.3e-2, DS 3.8e-2, UCM 7.5e-2, EUCM 2.5e-2, FOV
+2.2e-2; at a given start on the zoo cameras 2.1e-4 (pinhole_aniso) ... 7.7e-3
+(kb_negative).
 """
 import ctypes
 import functools
@@ -20,11 +27,11 @@ import numpy as np
 import pytest
 import torch
 
+import camera_zoo as Z
 import oracle
 import point_jacobian_ref as PJ
 import triangulation_ref as T
-from apex_camera_models import (Resolution, _lib, samples, tracks_from_dense, triangulate)
-from apex_camera_models.camera import MODEL_CLASSES
+from apex_camera_models import _lib, samples, tracks_from_dense, triangulate
 from apex_camera_models.optimizer import Pose, TriangulationConfig
 
 pytestmark = pytest.mark.gpu
@@ -35,8 +42,8 @@ START_SIZES = (1, 63, 64, 65, 257, 1000)
 
 
 def _model(mid):
-    params, (w, h) = samples.SAMPLES[mid]
-    return MODEL_CLASSES[samples.MODEL_NAMES[mid]]._from_params(list(params), Resolution(w, h))
+    """mid: a model id (its sample camera) or a zoo camera's name, here and below"""
+    return Z.device_model(mid)
 
 
 def _dev(a, dtype):
@@ -86,25 +93,27 @@ def _prefix(kind, mid, n, noise_px=0.0):
 # ------------------------------------------------------------ 1. start only
 @functools.lru_cache(maxsize=None)
 def _midpoint_reference(mid, noise_px=0.0):
-    """The numpy midpoint of the first 1000 wide-rig points (shared)."""
-    _, offsets, view, uv = _prefix("wide", mid, 1000, noise_px)
-    return T.midpoint("wide", mid, offsets, view, uv)
+    """The numpy midpoint of the first 1000 points of the camera's rig (shared)."""
+    kind = T.rig_kind(mid)
+    _, offsets, view, uv = _prefix(kind, mid, 1000, noise_px)
+    return T.midpoint(kind, mid, offsets, view, uv)
 
 
-@pytest.mark.parametrize("mid", [KB, DS])
+@pytest.mark.parametrize("mid", ALL_MODELS)
 def test_midpoint_start_matches_numpy(mid):
+    kind = T.rig_kind(mid)
     X_ref, cond, usable = _midpoint_reference(mid)
-    _, _, centres = T.rig("wide")
+    _, _, centres = T.rig(kind)
     params, (w, h) = samples.SAMPLES[mid]
-    _, offsets, view, uv = _prefix("wide", mid, 1000)
+    _, offsets, view, uv = _prefix(kind, mid, 1000)
     _, st = oracle.unproject(mid, params, w, h, uv)
     assert (st == 0).all() and (usable == np.diff(offsets)).all()
     assert cond.max() <= 2000.0, cond.max()
     cmax = np.linalg.norm(centres, axis=1).max()
     worst = 0.0
     for n in START_SIZES:
-        _, offs, vw, obs = _prefix("wide", mid, n)
-        X, status, cost, nv, info = _c_triangulate(mid, T.poses12("wide"), offs, vw, obs,
+        _, offs, vw, obs = _prefix(kind, mid, n)
+        X, status, cost, nv, info = _c_triangulate(mid, T.poses12(kind), offs, vw, obs,
                                                    max_iterations=0)
         assert (status == _lib.TRI_OK).all(), (n, status)
         assert (nv == np.diff(offs)).all()
@@ -140,12 +149,14 @@ N_NOISY = 4099
 
 @functools.lru_cache(maxsize=None)
 def _noisy_run(mid):
-    """The default call on the noisy wide rig (shared by tests 3 and 4)."""
+    """The default call on the camera's noisy rig (the wide one for KB and
+    DS; shared by tests 3 and 4)."""
+    kind = T.rig_kind(mid)
     params, (w, h) = samples.SAMPLES[mid]
-    _, offsets, view, uv = _prefix("wide", mid, N_NOISY, 0.5)
+    _, offsets, view, uv = _prefix(kind, mid, N_NOISY, 0.5)
     _, st = oracle.unproject(mid, params, w, h, uv)
     assert (st == 0).all(), "a noisy pixel does not unproject on the oracle"
-    return _c_triangulate(mid, T.poses12("wide"), offsets, view, uv)
+    return _c_triangulate(mid, T.poses12(kind), offsets, view, uv)
 
 
 @pytest.mark.parametrize("mid", [KB, DS])
@@ -165,13 +176,14 @@ def test_noisy_optimum_matches_scipy(mid):
 
 
 # ------------------------------------- 4. information, cost, n_valid
-@pytest.mark.parametrize("mid", [KB, DS])
+@pytest.mark.parametrize("mid", ALL_MODELS)
 def test_information_cost_and_n_valid(mid):
     n = 250
+    kind = T.rig_kind(mid)
     X, status, cost, nv, info = _noisy_run(mid)
-    _, offsets, view, uv = _prefix("wide", mid, n, 0.5)
-    R, t, _ = T.rig("wide")
-    p = T.camera_points("wide", X[:n], offsets, view)
+    _, offsets, view, uv = _prefix(kind, mid, n, 0.5)
+    R, t, _ = T.rig(kind)
+    p = T.camera_points(kind, X[:n], offsets, view)
     have = PJ.reference_rows(mid, p)
     assert have.all(), "a projection at the returned X is not Ok on the oracle"
     Jp = PJ.mp_jacobians(mid, p)                       # (M, 2, 3)
@@ -198,6 +210,76 @@ def test_information_cost_and_n_valid(mid):
             worst = max(worst, err / bound)
             assert err <= bound, (i, got, exact, err / bound)
     print(f"information / cost {samples.MODEL_NAMES[mid]}: worst |gpu - exact| / bound = {worst:.3e}")
+
+
+ZOO_N, ZOO_N_REFERENCE = 1000, 300
+
+
+@pytest.mark.parametrize("name", Z.SOLVER_SUBSET)
+def test_information_cost_and_n_valid_at_a_given_start(name):
+    """ACM_TRI_USE_INITIAL with max_iterations = 0 on a zoo camera: one
+    evaluation at the given points (the truth moved by (0.01, -0.01, 0.02)),
+    0.5 px noise, NaN / Inf pixels and out-of-range view indices put in at
+    fixed places.  1000 points in one call (across the wave and the workgroup
+    seams); n_valid and the status of every point, information and cost of
+    the first 300 against the 50-digit terms; the first 257 alone give the
+    same bits."""
+    kind = T.rig_kind(name)
+    truth, offsets, view, uv = _prefix(kind, name, ZOO_N, 0.5)
+    view, uv = np.array(view), np.array(uv)
+    j = np.arange(len(view))
+    uv[j % 37 == 5, 0] = np.nan
+    uv[j % 53 == 7, 1] = np.inf
+    view[j % 41 == 11] = -1
+    view[j % 43 == 13] = T.K_VIEWS
+    usable = np.isfinite(uv).all(axis=1) & (view >= 0) & (view < T.K_VIEWS)
+    start = truth + np.array([0.01, -0.01, 0.02])
+    poses = T.poses12(kind)
+    X, status, cost, nv, info = _c_triangulate(name, poses, offsets, view, uv, max_iterations=0,
+                                               initial=start)
+    m257 = offsets[257]
+    alone = _c_triangulate(name, poses, offsets[:258], view[:m257], uv[:m257], max_iterations=0,
+                           initial=start[:257])
+    for x, y in zip((X, status, cost, nv, info), alone):
+        assert x[:257].tobytes() == y.tobytes(), "the first 257 points differ when run alone"
+    want_nv = np.add.reduceat(usable.astype(np.int64), offsets[:-1])
+    assert (nv == want_nv).all(), np.nonzero(nv != want_nv)[0][:5]
+    few = want_nv < 2
+    assert few.any() and (status[few] == _lib.TRI_TOO_FEW_OBSERVATIONS).all()
+    assert (status[~few] == _lib.TRI_OK).all(), np.unique(status, return_counts=True)
+    assert np.isnan(cost[few]).all() and (info[few] == 0.0).all()
+    assert X[~few].tobytes() == start[~few].tobytes(), "max_iterations = 0 moved a point"
+    n = ZOO_N_REFERENCE
+    mref = offsets[n]
+    R, t, _ = T.rig(kind)
+    safe_view = np.where(usable, view, 0)[:mref]
+    p = np.einsum("mij,mj->mi", R[safe_view], start[T.point_of(offsets[: n + 1])]) + t[safe_view]
+    have = PJ.reference_rows(name, p)
+    assert have[usable[:mref]].all(), "a projection at the start is not Ok on the oracle"
+    Jp = PJ.mp_jacobians(name, p)
+    uv_exact = PJ.mp_project(name, p, have)
+    J = np.einsum("mab,mbc->mac", Jp, R[safe_view])
+    r = uv_exact - uv[:mref]
+    worst = 0.0
+    for i in np.nonzero(~few[:n])[0]:
+        rows = np.arange(offsets[i], offsets[i + 1])
+        rows = rows[usable[rows]]
+        Ji, ri = J[rows], r[rows]
+        k = 0
+        checks = []
+        for a in range(3):
+            for b in range(a, 3):
+                terms = np.concatenate([Ji[:, 0, a] * Ji[:, 0, b], Ji[:, 1, a] * Ji[:, 1, b]])
+                checks.append((info[i, k], terms))
+                k += 1
+        checks.append((cost[i], 0.5 * np.concatenate([ri[:, 0] ** 2, ri[:, 1] ** 2])))
+        for got, terms in checks:
+            exact, mag = math.fsum(terms), math.fsum(np.abs(terms))
+            bound = max(1e-10 * abs(exact), 1e-13 * mag)
+            err = abs(got - exact)
+            worst = max(worst, err / bound)
+            assert err <= bound, (i, got, exact, err / bound)
+    print(f"information / cost at a given start {name}: worst |gpu - exact| / bound = {worst:.3e}")
 
 
 # ------------------------------------------------------------ 5. statuses

@@ -7,7 +7,19 @@ Rigs (K = 6 views, world -> camera p = R X + t, t = -R c):
   narrow c_k = (0.15 (k - 2.5), 0.05 ((k mod 3) - 1), 0.02 (k mod 2)),
          R_k = Exp((0.01 ((k mod 3) - 1), -0.015 (k - 2.5), 0.02 (k mod 2)));
          points x in +-0.3, y in +-0.2, z in [2, 4)
-Each track is a random subset of 2..6 views, in view order.
+  medium c_k = (0.3 (k - 2.5), 0.1 ((k mod 3) - 1), 0.04 (k mod 2)),
+         R_k = Exp((0.02 ((k mod 3) - 1), -0.03 (k - 2.5), 0.02 (k mod 2)));
+         the narrow rig's points: a baseline long enough that the midpoint's
+         cond(A) stays below 2000, with every pixel inside the image of the
+         models that reject pixels outside it (Pinhole, RadTan)
+  tight  c_k = (0.03 (k - 2.5), 0.02 ((k mod 3) - 1), 0.01 (k mod 2)),
+         R_k = Exp((0.004 ((k mod 3) - 1), -0.004 (k - 2.5), 0.01 (k mod 2)));
+         points x, y in +-0.1, z in [2, 4): |x / z| stays below 0.1, for a
+         bounded image whose principal point is close to its border
+rig_kind(mid) names the widest of them on which camera `mid` sees every point.
+Each track is a random subset of 2..6 views, in view order.  `mid` below is a
+camera key (camera_zoo.camera_of): a model id for its sample camera, or a zoo
+camera's name.
 
 midpoint(): the numpy restatement of acm_triangulate's start from
 oracle.unproject rays: d = R^T ray, c = -R^T t, A = sum (I - d d^T),
@@ -20,7 +32,7 @@ import functools
 import numpy as np
 
 import oracle
-from apex_camera_models import samples
+from camera_zoo import camera_of
 
 K_VIEWS = 6
 SEED = 20251205
@@ -46,6 +58,12 @@ def rig(kind):
         if kind == "wide":
             cs.append([0.4 * a, 0.15 * b, 0.05 * c])
             Rs.append(exp_so3([0.03 * b, -0.04 * a, 0.02 * c]))
+        elif kind == "medium":
+            cs.append([0.3 * a, 0.1 * b, 0.04 * c])
+            Rs.append(exp_so3([0.02 * b, -0.03 * a, 0.02 * c]))
+        elif kind == "tight":
+            cs.append([0.03 * a, 0.02 * b, 0.01 * c])
+            Rs.append(exp_so3([0.004 * b, -0.004 * a, 0.01 * c]))
         else:
             cs.append([0.15 * a, 0.05 * b, 0.02 * c])
             Rs.append(exp_so3([0.01 * b, -0.015 * a, 0.02 * c]))
@@ -54,6 +72,16 @@ def rig(kind):
     for arr in (R, t, c):
         arr.setflags(write=False)
     return R, t, c
+
+
+# cameras that reject pixels outside the image and do not see the whole wide scene
+_RIG_KIND = {0: "medium", 1: "medium", "radtan_k3_tangential": "medium", "pinhole_aniso": "tight"}
+
+
+def rig_kind(mid):
+    """The rig and scene the tests use for camera `mid`; observations() asserts
+    that every projection on it is Ok."""
+    return _RIG_KIND.get(mid, "wide")
 
 
 def poses12(kind):
@@ -70,6 +98,8 @@ def scene(kind):
     rng = np.random.default_rng(SEED)
     if kind == "wide":
         xy = rng.uniform(-1.0, 1.0, (N_MAX, 2))
+    elif kind == "tight":
+        xy = rng.uniform(-1.0, 1.0, (N_MAX, 2)) * [0.1, 0.1]
     else:
         xy = rng.uniform(-1.0, 1.0, (N_MAX, 2)) * [0.3, 0.2]
     z = rng.uniform(2.0, 4.0, N_MAX)
@@ -97,12 +127,12 @@ def camera_points(kind, X, offsets, view):
 
 @functools.lru_cache(maxsize=None)
 def observations(kind, mid, noise_px=0.0):
-    """(M, 2) oracle projections of scene(kind) through model `mid`'s sample
-    camera (+ N(0, noise_px) pixels, seed SEED + 1).  Asserts that every
-    projection is Ok on the oracle."""
-    params, (w, h) = samples.SAMPLES[mid]
+    """(M, 2) oracle projections of scene(kind) through camera `mid`
+    (+ N(0, noise_px) pixels, seed SEED + 1).  Asserts that every projection
+    is Ok on the oracle."""
+    model, params, (w, h) = camera_of(mid)
     X, offsets, view = scene(kind)
-    uv, st, _ = oracle.project(mid, params, w, h, camera_points(kind, X, offsets, view))
+    uv, st, _ = oracle.project(model, params, w, h, camera_points(kind, X, offsets, view))
     assert (st == 0).all(), (kind, mid, "an oracle projection of the rig is not Ok")
     if noise_px:
         uv = uv + np.random.default_rng(SEED + 1).normal(0.0, noise_px, uv.shape)
@@ -114,9 +144,9 @@ def midpoint(kind, mid, offsets, view, uv):
     """The numpy midpoint per track: (X0 (N, 3), cond(A) (N,), usable (N,)).
     Unusable observations (oracle unprojection not Ok, non-finite pixel, view
     out of range) are skipped; X0 is NaN where fewer than 2 are usable."""
-    params, (w, h) = samples.SAMPLES[mid]
+    model, params, (w, h) = camera_of(mid)
     R, t, _ = rig(kind)
-    rays, st = oracle.unproject(mid, params, w, h, np.nan_to_num(uv, nan=-1.0))
+    rays, st = oracle.unproject(model, params, w, h, np.nan_to_num(uv, nan=-1.0))
     ok = (st == 0) & np.isfinite(uv).all(axis=1) & (view >= 0) & (view < K_VIEWS)
     n = len(offsets) - 1
     X0 = np.full((n, 3), np.nan)
@@ -144,10 +174,10 @@ def midpoint(kind, mid, offsets, view, uv):
 def residuals(kind, mid, views, uvs, X):
     """Oracle residuals (2 m,) of one track at X; 0 where the projection is
     not Ok (as tests/test_gpu_pose.py's scipy reference)."""
-    params, (w, h) = samples.SAMPLES[mid]
+    model, params, (w, h) = camera_of(mid)
     R, t, _ = rig(kind)
     p = R[views] @ np.asarray(X) + t[views]
-    uv, st, _ = oracle.project(mid, params, w, h, p)
+    uv, st, _ = oracle.project(model, params, w, h, p)
     r = uv - uvs
     r[(st != 0) | ~np.isfinite(r).all(axis=1)] = 0.0
     return r.ravel()
