@@ -2170,8 +2170,10 @@ struct RansacShared {
 };
 
 // The unit bearing of pixel (u, v); false: not usable.  The model's
-// unprojection decides Ok; for UCM the bearing is the projection's inverse
-// (see below).  RADTAN_POLISH: the two-view solver's extra Newton steps.
+// unprojection decides Ok; for UCM, FOV and KB the bearing is the projection's
+// inverse, which also refuses a FOV pixel no ray projects to and a KB pixel
+// whose iteration fails (see below; tests/bearing_ref.py is the numpy form).
+// RADTAN_POLISH: the two-view solver's extra Newton steps.
 template <class TagT, bool RADTAN_POLISH>
 __device__ __forceinline__ bool pixel_bearing(const Cam<double>& c, double u, double v, double& rx,
                                               double& ry, double& rz) {
@@ -2191,6 +2193,66 @@ __device__ __forceinline__ bool pixel_bearing(const Cam<double>& c, double u, do
         rx = coeff * mx;
         ry = coeff * my;
         rz = coeff - xi;
+    }
+    if constexpr (std::is_same<TagT, Tag<Fov>>::value) {
+        // Fov::unproject divides by cos(rd w) as the reference does: beyond
+        // 90 degrees (rd w > pi / 2) that is negative and the normalised ray
+        // is the antipode of the one that projects to (u, v); from rd w = pi
+        // on no ray projects to the pixel, yet the status is Ok.  The bearing
+        // is the projection's inverse, (m sin(rd w) / (rd 2 tan(w/2)),
+        // cos(rd w)): the same ray wherever cos > 0, continuous through 90
+        // degrees.  The axis and 2 tan(w/2) ~ 0 keep the unprojection's ray.
+        const double mx = (u - c.p[2]) / c.p[0], my = (v - c.p[3]) / c.p[1];
+        const double rd = sqrt_rn(mx * mx + my * my), mul2 = 2.0 * c.p[8];  // p[8] = tan(w / 2)
+        if (mul2 > kEpsSqrt && rd > kEpsSqrt) {
+            const double psi = rd * c.p[4];
+            if (!(psi < kPi)) return false;  // also NaN and Inf
+            double s, co;
+            sincos_0_2(psi, &s, &co);
+            const double ru = s / (rd * mul2);
+            rx = mx * ru;
+            ry = my * ru;
+            rz = co;
+        }
+    }
+    if constexpr (std::is_same<TagT, Tag<KannalaBrandt>>::value) {
+        // KannalaBrandt::unproject clamps ru = |m| to pi / 2 as the reference
+        // does and solves theta_d(theta) = pi / 2 for every pixel beyond, so
+        // its ray there is not the one that projects to (u, v) (58 px off in
+        // the sample camera's corners); and it ends its Newton iteration at
+        // |delta| < 1e-6, which under strong distortion leaves theta 5e-11
+        // rad off.  The status above decides as for every model; the bearing
+        // is the projection's inverse: the reference's iteration on
+        // theta_d(theta) = ru without the clamp (from theta = ru, at most 10
+        // steps, until |delta| < 1e-6) and one more step; a pixel it does
+        // not converge for is unusable.  ru <= 1e-6 is the axis pixel here
+        // (Ok only for ru = 0) and keeps the unprojection's ray.
+        const double mx = (u - c.p[2]) / c.p[0], my = (v - c.p[3]) / c.p[1];
+        const double ru = sqrt_rn(mx * mx + my * my);
+        if (ru > 1e-6) {
+            const double k1 = c.p[4], k2 = c.p[5], k3 = c.p[6], k4 = c.p[7];
+            double theta = ru;
+            bool converged = false;
+#pragma unroll 1
+            for (int i = 0; i <= 10; ++i) {  // the last round is the extra step
+                const double t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+                const double a1 = k1 * t2, a2 = k2 * t4, a3 = k3 * t6, a4 = k4 * t8;
+                const double f = theta * (1.0 + a1 + a2 + a3 + a4) - ru;
+                const double fp = 1.0 + (3.0 * a1) + (5.0 * a2) + (7.0 * a3) + (9.0 * a4);
+                if (!converged && (i == 10 || fabs(fp) < kEps)) break;
+                const double delta = f / fp;
+                theta -= delta;
+                if (converged) break;
+                converged = fabs(delta) < 1e-6;
+            }
+            if (!converged) return false;
+            double s, co;
+            sincos_0_2(theta, &s, &co);
+            const double q = s / ru;
+            rx = mx * q;
+            ry = my * q;
+            rz = co;
+        }
     }
     if constexpr (RADTAN_POLISH && std::is_same<TagT, Tag<RadTan>>::value) {
         // RadTan::unproject ends its Newton iteration, as the reference does,

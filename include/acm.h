@@ -720,12 +720,31 @@ ACM_API int acm_pose_optimize_batch(const acm_camera *cam, size_t n_views, acm_p
  * An observation is usable iff its pixel is finite, obs_point[j] lies in
  * [0, n_points), its world point is finite and the unprojection of the pixel
  * (acm_unproject's default numerics, as acm_triangulate's midpoint start) is
- * Ok with a finite direction; its bearing f is that ray, normalised.  One
- * model differs: the UCM unprojection keeps the reference's denominator
- * 1 - r^2, so its ray is not the one that projects to the pixel (off by up to
- * 1.5e-2 rad on the sample camera) and no pose fits such bearings; for UCM
- * that unprojection still decides Ok, and f is the projection's inverse, the
- * same formula with 1 + r^2.
+ * Ok with a finite direction; its bearing f is that ray, normalised.  Three
+ * models differ, each because the unprojection keeps a behaviour of the
+ * reference under which its ray is not the one that projects to the pixel; in
+ * each that unprojection still decides Ok and f is the projection's inverse.
+ * UCM: the unprojection's denominator is 1 - r^2 (off by up to 1.5e-2 rad on
+ * the sample camera; no pose fits such bearings); f is the same formula with
+ * 1 + r^2.
+ * FOV: the unprojection divides by cos(rd w), rd = |m|, which is negative
+ * beyond 90 degrees (rd w > pi / 2) and makes its normalised ray the antipode
+ * of the true one; f = (mx s / (rd 2 tan(w/2)), my s / (rd 2 tan(w/2)), c),
+ * (s, c) = sincos(rd w), normalised: the same ray wherever c > 0, continuous
+ * through 90 degrees, z < 0 beyond.  A pixel with rd w >= pi is the image of
+ * no ray: not usable.  (On the axis, rd <= sqrt(eps), and for 2 tan(w/2) <=
+ * sqrt(eps) f is the unprojection's ray.)
+ * KB: the unprojection clamps ru = |m| to pi / 2 and solves theta_d(theta) =
+ * pi / 2 for every pixel beyond (58 px off in the sample camera's corners),
+ * and stops its Newton iteration at |delta| < 1e-6 (up to 5e-11 rad under
+ * strong distortion); f = (mx sin(theta) / ru, my sin(theta) / ru,
+ * cos(theta)) with theta from the same iteration on theta_d(theta) = ru
+ * unclamped (from theta = ru, at most 10 steps, until |delta| < 1e-6) and one
+ * more step.  A pixel for which that iteration does not converge is not
+ * usable.  (ru <= 1e-6: the unprojection's ray.)
+ * RadTan's ray is the unprojection's, which ends its Newton iteration at a
+ * residual of 1e-6: up to 1e-6 rad (6e-4 px) from the true direction here;
+ * the two-view solvers polish it (acm_relative_pose_batch).
  * Anything else is skipped -- an out-of-range index is never dereferenced and
  * is no error of the call.  n_usable (nullable) receives the count per view.
  * The view's records (X, Y, Z, fx, fy, fz; 48 B) are built once: in LDS for a
@@ -858,9 +877,11 @@ ACM_API int acm_pose_estimate_batch(const acm_camera *cam, size_t n_views, acm_p
  *
  * A match is usable iff both pixels are finite and both unprojections
  * (acm_unproject's default numerics) are Ok with a finite direction; its
- * bearings are those rays, normalised, with two exceptions in which that
- * unprojection still decides Ok: for UCM the bearing is the projection's
- * inverse, as acm_pose_estimate_batch documents; for RadTan, whose
+ * bearings are those rays, normalised, with four exceptions in which that
+ * unprojection still decides Ok: for UCM, FOV and KB the bearing is the
+ * projection's inverse, and a FOV pixel with rd w >= pi or a KB pixel whose
+ * Newton iteration does not converge is not usable, all as
+ * acm_pose_estimate_batch documents; for RadTan, whose
  * unprojection ends its Newton iteration once the distortion residual is
  * below 1e-6 and so misses the direction that projects to the pixel by up to
  * 1e-6 rad (an exact pair of 8 matches finds no model with such rays at a
@@ -1014,8 +1035,8 @@ ACM_API int acm_relative_pose_batch(const acm_camera *cam, size_t n_pairs, acm_p
  *
  * acm_homography_batch: RANSAC over that solver, one 256-lane workgroup per
  * view pair, all pairs in one launch.  The matches (CSR by pair, clamped
- * offsets), the usable-match rule and the bearings (UCM's inverse of the
- * projection, RadTan polished), the records of 48 B in LDS for a pair of at
+ * offsets), the usable-match rule and the bearings (UCM's, FOV's and KB's
+ * inverse of the projection, RadTan polished), the records of 48 B in LDS for a pair of at
  * most ACM_HOMOGRAPHY_STAGE_MATCHES matches and in the workspace beyond, and
  * n_usable are acm_relative_pose_batch's.
  *

@@ -11,8 +11,8 @@ seen through test_gpu_relative_pose.true_pose, a motion that differs per pair
 -- x in [-1, 1), y in [-0.7, 0.7) for the zero-noise test, which fits every
 model's image, x, y in [-4, 4) for the noisy tests of the two fisheye models.
 The pixels are the oracle's projections, the bearings the numpy side uses are
-the oracle's unprojections with UCM's and RadTan's bearing rule
-(test_gpu_relative_pose.bearings).
+tests/bearing_ref.py's (the oracle's unprojection under the kernel's bearing
+rule, RadTan polished; test_gpu_relative_pose.bearings).
 
 A gross outlier is drawn by rejection: its transfer sine at the true H
 exceeds 10 sin(inlier_angle).
@@ -46,6 +46,7 @@ import numpy as np
 import pytest
 import torch
 
+import camera_zoo as Z
 import homography_ref as G
 import oracle
 import relative_pose_ref as Q
@@ -177,33 +178,34 @@ def plane_points(rng, m, half_x, half_y):
 
 
 @functools.lru_cache(maxsize=None)
-def scene(mid, counts, wide=False):
+def scene(key, counts, wide=False):
     """(offsets, uv_a, uv_b, X): exact pixels of points on the plane, pair k
-    seen through true_pose(mid, k); X are the points in camera A's frame."""
-    rng = np.random.default_rng(20261024 + mid)
+    seen through true_pose(key, k); X are the points in camera A's frame.
+    key: a model id (its sample camera) or a zoo camera's name."""
+    rng = np.random.default_rng(20261024 + Z.camera_of(key)[0])
     offsets = np.zeros(len(counts) + 1, dtype=np.int64)
     offsets[1:] = np.cumsum(counts)
     m = int(offsets[-1])
     X = plane_points(rng, m, 4.0, 4.0) if wide else plane_points(rng, m, 1.0, 0.7)
-    uv_a = project(mid, X)
+    uv_a = project(key, X)
     uv_b = np.empty_like(uv_a)
     for k in range(len(counts)):
-        Rm, t = true_pose(mid, k)
+        Rm, t = true_pose(key, k)
         sl = slice(offsets[k], offsets[k + 1])
-        uv_b[sl] = project(mid, X[sl] @ Rm.T + t)
+        uv_b[sl] = project(key, X[sl] @ Rm.T + t)
     for arr in (offsets, uv_a, uv_b, X):
         arr.setflags(write=False)
     return offsets, uv_a, uv_b, X
 
 
-def run(mid, offsets, uv_a, uv_b, bare=False, **kw):
+def run(key, offsets, uv_a, uv_b, bare=False, **kw):
     """The C call; numpy outputs, every output prefilled with a sentinel.
     bare: without the nullable outputs."""
     L = _lib.load()
     c = _lib.HomographyConfig()
     L.acm_homography_batch_default_config(ctypes.byref(c))
-    for key, v in kw.items():
-        setattr(c, key, v)
+    for name, v in kw.items():
+        setattr(c, name, v)
     k, m = len(offsets) - 1, len(uv_a)
     dev = "cuda"
     o_t = torch.as_tensor(np.array(offsets), device=dev)
@@ -221,7 +223,7 @@ def run(mid, offsets, uv_a, uv_b, bare=False, **kw):
     mask = torch.full((m + 1,), 77, dtype=torch.uint8, device=dev)
     ws_bytes = L.acm_homography_batch_workspace_size(k, m)
     ws = torch.full(((ws_bytes + 7) // 8 + 1,), -3.0, dtype=torch.float64, device=dev)
-    cam = _model(mid).acm_camera()
+    cam = _model(key).acm_camera()
     opt = [None] * 7 if bare else [x.data_ptr() for x in (poses, planes, n_sol, n_front, tau, mask,
                                                            n_use)]
     rc = L.acm_homography_batch(

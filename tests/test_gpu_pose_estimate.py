@@ -35,7 +35,8 @@ import numpy as np
 import pytest
 import torch
 
-import oracle
+import bearing_ref as BR
+import camera_zoo as Z
 import pose_estimation_ref as P
 import test_gpu_pose_batch as B
 from apex_camera_models import _lib, samples
@@ -109,12 +110,9 @@ def test_p3p_degenerate_triplets():
 
 
 # ------------------------------------------------- acm_pose_estimate_batch
-def _params(mid):
-    return samples.SAMPLES[mid]
-
-
 def _angle_of(mid, threshold_px):
-    params, _ = _params(mid)
+    """mid: a model id (its sample camera) or a zoo camera's name, here and below"""
+    _, params, _ = Z.camera_of(mid)
     return math.atan(threshold_px / min(params[0], params[1]))
 
 
@@ -158,18 +156,13 @@ def _dev(*arrays):
 
 
 def _records(mid, world, point, uv):
-    """numpy restatement of the usable rule: (X (m, 3), f (m, 3), usable (m,))
-    with the oracle's unprojection.  For UCM that ray is not the kernel's
-    bearing (the module docstring); only `usable` is compared for it."""
-    params, (w, h) = _params(mid)
+    """The usable rule: (X (m, 3), f (m, 3), usable (m,)) with the bearings of
+    tests/bearing_ref.py (no RadTan polish in pose estimation)."""
     point = np.asarray(point, dtype=np.int64)
     in_range = (point >= 0) & (point < len(world))
     X = np.asarray(world)[np.where(in_range, point, 0)]
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        rays, st = oracle.unproject(mid, params, w, h, np.where(np.isfinite(uv), uv, 0.0))
-        f = rays / np.linalg.norm(rays, axis=1)[:, None]
-    usable = (in_range & np.isfinite(uv).all(axis=1) & np.isfinite(X).all(axis=1) & (st == 0) &
-              np.isfinite(f).all(axis=1))
+    f, pixel_ok = BR.bearings(mid, uv, False)
+    usable = in_range & np.isfinite(X).all(axis=1) & pixel_ok
     return X, f, usable
 
 

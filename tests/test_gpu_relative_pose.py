@@ -11,8 +11,8 @@ in [-1, 1), y in [-0.7, 0.7), z in [2.5, 6)) for the zero-noise test, a wide
 one (x, y in [-4, 4), z in [1.5, 6)) for the noisy tests of the two fisheye
 models, because two-view geometry from a narrow field of view is badly
 conditioned under noise.  The pixels are the oracle's projections, the
-bearings the numpy side uses are the oracle's unprojections (for UCM the
-projection's inverse, for RadTan polished by two Newton steps, as the kernel).
+bearings the numpy side uses are tests/bearing_ref.py's (the oracle's
+unprojection under the kernel's bearing rule, RadTan polished).
 
 A gross outlier is drawn by rejection: its epipolar sine at the true pose
 exceeds 10 sin(inlier_angle).  The epipolar constraint is one-dimensional, so
@@ -41,10 +41,11 @@ import numpy as np
 import pytest
 import torch
 
+import bearing_ref as BR
+import camera_zoo as Z
 import oracle
 import relative_pose_ref as Q
-from apex_camera_models import Resolution, _lib, samples
-from apex_camera_models.camera import MODEL_CLASSES
+from apex_camera_models import _lib, samples
 from apex_camera_models.optimizer import (RelativePoseConfig, estimate_relative_poses,
                                           relative_pose_8pt, triangulate, two_view_tracks)
 from test_relative_pose_ref import CSRC, DRIVER, check_against_reference
@@ -60,13 +61,13 @@ NOISY_COUNTS = (40, 100, 300, 1025)
 NOISE_PX, THRESHOLD_PX = 0.5, 3.0
 
 
-def _model(mid):
-    params, (w, h) = samples.SAMPLES[mid]
-    return MODEL_CLASSES[samples.MODEL_NAMES[mid]]._from_params(list(params), Resolution(w, h))
+def _model(key):
+    """key: a model id (its sample camera) or a zoo camera's name, here and below"""
+    return Z.device_model(key)
 
 
-def _angle_of(mid, threshold_px):
-    params, _ = samples.SAMPLES[mid]
+def _angle_of(key, threshold_px):
+    _, params, _ = Z.camera_of(key)
     return math.atan(threshold_px / min(params[0], params[1]))
 
 
@@ -166,78 +167,43 @@ def test_8pt_failures():
 
 
 # -------------------------------------------------- acm_relative_pose_batch
-def bearings(mid, uv):
-    """numpy restatement of the usable rule for one image: (f (m, 3), usable
-    (m,)) from the oracle's unprojection; for UCM the bearing is the
-    projection's inverse, for RadTan that ray after two more Newton steps
-    (include/acm.h)."""
-    params, (w, h) = samples.SAMPLES[mid]
-    uv = np.asarray(uv, dtype=np.float64)
-    fin = np.isfinite(uv).all(axis=1)
-    safe = np.where(fin[:, None], uv, 0.0)
-    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-        rays, st = oracle.unproject(mid, params, w, h, safe)
-        if mid == UCM:
-            alpha = params[4]
-            gamma, xi = 1.0 - alpha, alpha / (1.0 - alpha)
-            mx = (safe[:, 0] - params[2]) / params[0] * gamma
-            my = (safe[:, 1] - params[3]) / params[1] * gamma
-            r2 = mx * mx + my * my
-            coeff = (xi + np.sqrt(1.0 + (1.0 - xi * xi) * r2)) / (1.0 + r2)
-            rays = np.stack([coeff * mx, coeff * my, coeff - xi], axis=1)
-        if mid == RADTAN:
-            # two more Newton steps on the distortion, as the kernel takes
-            k1, k2, p1, p2, k3 = params[4:9]
-            tx, ty = (safe[:, 0] - params[2]) / params[0], (safe[:, 1] - params[3]) / params[1]
-            x, y = rays[:, 0] / rays[:, 2], rays[:, 1] / rays[:, 2]
-            for _ in range(2):
-                r2 = x * x + y * y
-                radial = 1.0 + k1 * r2 + k2 * r2 ** 2 + k3 * r2 ** 3
-                ex = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x) - tx
-                ey = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y - ty
-                dr = 2.0 * (k1 + 2.0 * k2 * r2 + 3.0 * k3 * r2 ** 2)
-                a00 = radial + dr * x * x + 2.0 * p1 * y + 6.0 * p2 * x
-                a01 = dr * x * y + 2.0 * p1 * x + 2.0 * p2 * y
-                a11 = radial + dr * y * y + 6.0 * p1 * y + 2.0 * p2 * x
-                det = a00 * a11 - a01 * a01
-                x, y = x - (a11 * ex - a01 * ey) / det, y - (a00 * ey - a01 * ex) / det
-            rays = np.stack([x, y, np.ones_like(x)], axis=1)
-        f = rays / np.linalg.norm(rays, axis=1)[:, None]
-    usable = fin & (st == 0) & np.isfinite(f).all(axis=1)
-    return f, usable
+def bearings(key, uv):
+    """The two-view solvers' bearing rule for one image, (f (m, 3), usable
+    (m,)): tests/bearing_ref.py with RadTan's polish."""
+    return BR.bearings(key, uv, True)
 
 
-def records(mid, uv_a, uv_b):
-    fa, ua = bearings(mid, uv_a)
-    fb, ub = bearings(mid, uv_b)
+def records(key, uv_a, uv_b):
+    fa, ua = bearings(key, uv_a)
+    fb, ub = bearings(key, uv_b)
     return fa, fb, ua & ub
 
 
-def true_pose(mid, k):
+def true_pose(key, k):
     """Pair k's true relative pose: a rotation of up to 0.2 rad and a baseline
-    of 0.3 .. 0.6 with a sideways and a forward part."""
-    rng = np.random.default_rng(977 * mid + k)
+    of 0.3 .. 0.6 with a sideways and a forward part (one sequence per model)."""
+    rng = np.random.default_rng(977 * Z.camera_of(key)[0] + k)
     w = rng.normal(0.0, 0.07, 3)
     t = np.array([rng.uniform(0.25, 0.45) * (1 if k % 2 else -1), rng.uniform(-0.2, 0.2),
                   rng.uniform(-0.3, 0.3)])
     return Q.exp_so3(w), t
 
 
-def project(mid, pts):
-    params, (w, h) = samples.SAMPLES[mid]
+def project(key, pts):
+    mid, params, (w, h) = Z.camera_of(key)
     uv, st, _ = oracle.project(mid, params, w, h, np.ascontiguousarray(pts))
     assert (st == 0).all()
     return uv
 
 
 @functools.lru_cache(maxsize=None)
-def scene(mid, counts, wide=False):
+def scene(key, counts, wide=False):
     """(offsets, uv_a, uv_b, X): exact pixels of a random scene, pair k seen
-    through true_pose(mid, k); X are the points in camera A's frame.  The
+    through true_pose(key, k); X are the points in camera A's frame.  The
     narrow scene fits every model's image; the wide one (up to 70 degrees off
     the axis, for the fisheye models) is what makes two-view geometry well
     conditioned under noise."""
-    rng = np.random.default_rng(20261020 + mid)
+    rng = np.random.default_rng(20261020 + Z.camera_of(key)[0])
     offsets = np.zeros(len(counts) + 1, dtype=np.int64)
     offsets[1:] = np.cumsum(counts)
     m = int(offsets[-1])
@@ -247,24 +213,24 @@ def scene(mid, counts, wide=False):
     else:
         X = np.column_stack([rng.uniform(-1.0, 1.0, m), rng.uniform(-0.7, 0.7, m),
                              rng.uniform(2.5, 6.0, m)])
-    uv_a = project(mid, X)
+    uv_a = project(key, X)
     uv_b = np.empty_like(uv_a)
     for k in range(len(counts)):
-        Rm, t = true_pose(mid, k)
+        Rm, t = true_pose(key, k)
         sl = slice(offsets[k], offsets[k + 1])
-        uv_b[sl] = project(mid, X[sl] @ Rm.T + t)
+        uv_b[sl] = project(key, X[sl] @ Rm.T + t)
     for arr in (offsets, uv_a, uv_b, X):
         arr.setflags(write=False)
     return offsets, uv_a, uv_b, X
 
 
-def run(mid, offsets, uv_a, uv_b, want_mask=True, want_usable=True, **kw):
+def run(key, offsets, uv_a, uv_b, want_mask=True, want_usable=True, **kw):
     """The C call; numpy outputs, every output prefilled with a sentinel."""
     L = _lib.load()
     c = _lib.RelativePoseConfig()
     L.acm_relative_pose_batch_default_config(ctypes.byref(c))
-    for key, v in kw.items():
-        setattr(c, key, v)
+    for name, v in kw.items():
+        setattr(c, name, v)
     k, m = len(offsets) - 1, len(uv_a)
     dev = "cuda"
     o_t = torch.as_tensor(np.array(offsets), device=dev)
@@ -277,7 +243,7 @@ def run(mid, offsets, uv_a, uv_b, want_mask=True, want_usable=True, **kw):
     mask = torch.full((m + 1,), 77, dtype=torch.uint8, device=dev)
     ws_bytes = L.acm_relative_pose_batch_workspace_size(k, m)
     ws = torch.full(((ws_bytes + 7) // 8 + 1,), -3.0, dtype=torch.float64, device=dev)
-    cam = _model(mid).acm_camera()
+    cam = _model(key).acm_camera()
     rc = L.acm_relative_pose_batch(
         ctypes.byref(cam), k, poses.data_ptr(), o_t.data_ptr(), m, a_t.data_ptr() if m else None,
         b_t.data_ptr() if m else None, ctypes.byref(c), status.data_ptr(), n_inl.data_ptr(),
