@@ -35,8 +35,11 @@
 //   * project<.., FAST = true> (the fused normal equations only): one
 //     reciprocal and products instead of the per-point divisions.
 // None of these feeds a status decision, so statuses are bit-exact
-// everywhere; values are held to 1e-10 relative (tests/test_gpu_parity.py,
-// observed ~1e-15).  project<.., EXACT = true> (acm_project with
+// everywhere.  Per-point values are held to 1e-10 relative
+// (tests/test_gpu_parity.py, observed ~1e-15); the FAST form has no per-point
+// output, so it is held through every entry of the fused normal equations,
+// and its valid count on every threshold probe
+// (tests/test_gpu_normal_equations.py).  project<.., EXACT = true> (acm_project with
 // ACM_EXACT_MATH, and undistort_image, whose bytes round() / floor() the
 // source coordinates) takes the IEEE sqrt / divisions and the correctly
 // rounded double-double atan2 of exact_math.hpp: KB and FOV projections and
@@ -51,12 +54,14 @@
 // not diverge on the rare failing point; the caller selects outputs.
 //
 // project<WJ, FAST>: FAST = true (used only by the fused normal-equations
-// kernel, whose sums are held to 1e-10 anyway and are summed in a different
-// order than the reference) replaces the divisions by a per-point denominator
-// with one reciprocal and multiplies: u, v, J within ~1 ulp of the exact
-// path.  Status decisions never depend on those divisions, so the validity
-// mask (and n_valid) stays bit-exact.  Every other caller uses FAST = false,
-// the reference's operation order.
+// kernel, whose sums are summed in a different order than the reference and
+// are held, entry by entry, to max(1e-10 |exact|, 1e-13 sum |terms|) of the
+// exactly summed 50-digit terms, tests/test_gpu_normal_equations.py) replaces
+// the divisions by a per-point denominator with one reciprocal and
+// multiplies: u, v, J within ~1 ulp of the exact path.  Status decisions
+// never depend on those divisions, so the validity mask (and n_valid) stays
+// bit-exact (the same file puts every threshold probe through this form).
+// Every other caller uses FAST = false, the reference's operation order.
 //
 // project<WJ, FAST, EXACT, PJ>: PJ = true (acm_project_point_jacobian and the
 // pose normal equations; WJ = false) also returns the 2 x 3 derivative with

@@ -397,7 +397,8 @@ typedef int (*acm_allreduce_fn)(void *ctx, double *device_buffer, size_t count,
 
 /* (r06) Grid-sampled correspondences by cell (acm_sample_points_cells):
  * cell c = i * num_cells_x + j of the row-major grid whose centres are
- * ((j + 0.5) * width / num_cells_x, (i + 0.5) * height / num_cells_y)
+ * ((j + 0.5) * (width / num_cells_x), (i + 0.5) * (height / num_cells_y))
+ * -- the f64 cell size first, then the product, each rounded once
  * (point_sampling.rs:56-78; width, height: the SAMPLED camera's
  * resolution).  A uint32 per point instead of the 16-B pixel: the cell
  * forms below recompute each pixel exactly as sample_points wrote it, so

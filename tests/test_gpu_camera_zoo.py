@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import camera_zoo as Z
+import normal_equations_ref as NE
 import oracle as O
 import point_jacobian_ref as R
 from _backends import GpuBackend, rel_err
@@ -301,3 +302,10 @@ def test_normal_equations(name, policy):
     assert np.abs(A - A0).max() <= TOL * np.abs(A0).max()
     assert np.abs(b - b0).max() <= TOL * max(np.abs(b0).max(), 1.0)
     assert abs(c - c0) <= TOL * max(abs(c0), 1.0)
+    # and every entry on its own, against the exact sum of the oracle's
+    # per-point terms: max(1e-10 |exact|, 1e-13 sum |terms|)
+    # (tests/normal_equations_ref.py)
+    want, mag, n_valid = NE.oracle_terms_exact(model, params, w, h, xyz, obs, policy)
+    assert n_valid == nv0
+    worst = NE.check(res.cpu().numpy(), want, mag, n_valid)
+    print(f"zoo normal equations {name} policy {policy}: worst |gpu - exact| / bound = {worst:.3e}")

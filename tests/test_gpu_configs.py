@@ -14,6 +14,7 @@ against the oracle (each well under a minute):
 import numpy as np
 import pytest
 
+import normal_equations_ref as NE
 import oracle as O
 from _backends import rel_err
 
@@ -70,6 +71,27 @@ def test_config3_kb_to_ds_conversion_9m():
     ref = np.concatenate([JtJ.ravel(), Jtr, [cost]])
     scale = np.maximum(np.abs(ref), np.abs(ref).max() * 1e-6)
     assert (np.abs(got[:-1] - ref) / scale).max() <= 1e-10
+    # every entry on its own (no floor), on a strided ~1M subsample: against
+    # the exact sum of the oracle's per-point terms
+    _check_every_entry_on_subsample(p, w, h, xyz, uv, 9, "config 3")
+
+
+def _check_every_entry_on_subsample(p, w, h, xyz, uv, stride, what):
+    """The fused DS normal equations of every stride-th correspondence, per
+    entry within max(1e-10 |exact|, 1e-13 sum |terms|) of math.fsum of the
+    oracle's per-point terms (tests/normal_equations_ref.py)."""
+    import torch
+    from apex_camera_models import factors
+    from apex_camera_models.camera import Resolution
+    sub = torch.arange(0, xyz.shape[0], stride, device="cuda")
+    xs, us = xyz[sub].contiguous(), uv[sub].contiguous()
+    out = torch.empty((6 * 6 + 6 + 2,), dtype=torch.float64, device="cuda")
+    factors.DoubleSphereCameraParamsFactor(xs, us, Resolution(w, h)).normal_equations(p, out)
+    want, mag, n_valid = NE.oracle_terms_exact(DS, p, w, h, xs.cpu().numpy(), us.cpu().numpy(), 0)
+    assert n_valid == len(sub)
+    worst = NE.check(out.cpu().numpy(), want, mag, n_valid)
+    print(f"{what}: DS normal equations on {len(sub)} correspondences, worst |gpu - exact| / "
+          f"bound = {worst:.3e}")
 
 
 @pytest.mark.parametrize("model", range(6))
@@ -168,6 +190,8 @@ def test_config5_kb_to_ds_on_92_9m_correspondences():
     ref = np.concatenate([JtJ.ravel(), Jtr, [cost]])
     scale = np.maximum(np.abs(ref), np.abs(ref).max() * 1e-6)
     assert (np.abs(got[:-1] - ref) / scale).max() <= 1e-10
+    # every entry on its own (no floor), on the same strided subsample
+    _check_every_entry_on_subsample(p, w, h, xyz, uv, 93, "config 5")
     # BASELINE config 5's f32-vs-f64 tolerance sweep at scale: the DS
     # projection at the optimum over all 92.9M correspondences in f32
     # (acm_project_f32) agrees with the f64 path on every status, and its

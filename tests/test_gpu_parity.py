@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import kat_suite
+import normal_equations_ref as NE
 import oracle as O
 from _backends import GpuBackend, rel_err
 
@@ -234,9 +235,34 @@ def test_normal_equations_vs_oracle(golden_dir, model, policy):
     assert np.abs(A - A0).max() <= TOL * np.abs(A0).max()
     assert np.abs(b - b0).max() <= TOL * max(np.abs(b0).max(), 1.0)
     assert abs(c - c0) <= TOL * max(abs(c0), 1.0)
+    # and every entry on its own, against the exact sum of the oracle's
+    # per-point terms: max(1e-10 |exact|, 1e-13 sum |terms|)
+    # (tests/normal_equations_ref.py)
+    want, mag, n_valid = NE.oracle_terms_exact(model, params, w, h, xyz, obs, policy)
+    assert n_valid == nv0
+    worst = NE.check(res.cpu().numpy(), want, mag, n_valid)
+    print(f"normal equations {model} policy {policy}: worst |gpu - exact| / bound = {worst:.3e}")
     # deterministic: a second evaluation is bit-identical
     res2 = f.normal_equations(params)
     assert torch.equal(res, res2)
+
+
+def _tuning_cell_problem(model):
+    """Points, observations, the oracle's sums and the exact sums of its
+    per-point terms: computed once per model, shared by every tuning cell
+    (not cached beyond the test: 60 MB per model)."""
+    from apex_camera_models import samples
+    params, (w, h) = samples.SAMPLES[model]
+    n = 1_234_567
+    xyz = samples.synthetic_points(n)
+    xyz = xyz[np.isfinite(xyz).all(1)]
+    uv0, st0, _ = O.project(model, params, w, h, xyz)
+    obs = np.where(np.isnan(uv0), 3.0, uv0) + 0.25
+    ref = O.normal_equations(model, params, w, h, xyz, obs, 0)
+    exact = NE.oracle_terms_exact(model, params, w, h, xyz, obs, 0)
+    for a in (xyz, obs, exact[0], exact[1]):
+        a.setflags(write=False)
+    return xyz, obs, ref, exact
 
 
 @pytest.mark.parametrize("model", range(7))
@@ -248,12 +274,9 @@ def test_normal_equations_every_tuning_cell(model):
     from apex_camera_models import _lib, factors, samples
     from apex_camera_models.camera import Resolution
     params, (w, h) = samples.SAMPLES[model]
-    n = 1_234_567
-    xyz = samples.synthetic_points(n)
-    xyz = xyz[np.isfinite(xyz).all(1)]
-    uv0, st0, _ = O.project(model, params, w, h, xyz)
-    obs = np.where(np.isnan(uv0), 3.0, uv0) + 0.25
-    A0, b0, c0, nv0 = O.normal_equations(model, params, w, h, xyz, obs, 0)
+    xyz, obs, (A0, b0, c0, nv0), (want, mag, n_valid) = _tuning_cell_problem(model)
+    assert n_valid == nv0
+    worst = 0.0
     f = factors.CameraParamsFactor.__subclasses__()[model](
         torch.as_tensor(xyz), torch.as_tensor(obs), Resolution(w, h))
     P = len(params)
@@ -274,6 +297,13 @@ def test_normal_equations_every_tuning_cell(model):
             assert np.abs(A - A0).max() <= TOL * np.abs(A0).max(), cell
             assert np.abs(b - b0).max() <= TOL * max(np.abs(b0).max(), 1.0), cell
             assert abs(c - c0) <= TOL * max(abs(c0), 1.0), cell
+            # every entry on its own, against the exact sums of the oracle's terms
+            try:
+                worst = max(worst, NE.check(res.cpu().numpy(), want, mag, n_valid))
+            except AssertionError as e:
+                raise AssertionError(f"tuning cell {cell}: {e}") from None
+        print(f"normal equations {model}, {len(cells)} tuning cells: worst |gpu - exact| / bound "
+              f"= {worst:.3e}")
     finally:
         L.acm_set_tuning(_lib.TUNE_NE_WAVES, 0)
         L.acm_set_tuning(_lib.TUNE_NE_UNROLL, 0)
