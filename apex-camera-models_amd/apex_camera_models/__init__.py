@@ -25,6 +25,9 @@ from .optimizer import (RelativePoseConfig, RelativePoseResult,  # noqa: E402
                         estimate_relative_poses, relative_pose_8pt, two_view_tracks)
 from .optimizer import (HomographyConfig, HomographyResult,  # noqa: E402
                         estimate_homographies, homography_4pt)
+from .optimizer import (SimilarityConfig, SimilarityResult, apply_similarity,  # noqa: E402
+                        estimate_similarities, similarity_3pt, similarity_compose,
+                        similarity_inverse, similarity_transform_poses)
 
 __all__ = [
     "camera", "factors", "util", "CameraModel", "CameraModelError", "DoubleSphereModel",
@@ -38,4 +41,6 @@ __all__ = [
     "RelativePoseConfig", "RelativePoseResult", "estimate_relative_poses", "relative_pose_8pt",
     "two_view_tracks",
     "HomographyConfig", "HomographyResult", "estimate_homographies", "homography_4pt",
+    "SimilarityConfig", "SimilarityResult", "estimate_similarities", "similarity_3pt",
+    "apply_similarity", "similarity_transform_poses", "similarity_compose", "similarity_inverse",
 ]

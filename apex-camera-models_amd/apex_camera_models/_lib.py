@@ -182,6 +182,26 @@ HOMOGRAPHY_OK, HOMOGRAPHY_TOO_FEW_MATCHES, HOMOGRAPHY_NO_MODEL = 0, 1, 2
 HOMOGRAPHY_STAGE_MATCHES = 1024
 
 
+class SimilarityConfig(ctypes.Structure):
+    """acm_similarity_config (include/acm.h)."""
+    _fields_ = [
+        ("n_hypotheses", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("inlier_distance", ctypes.c_double),
+        ("min_inliers", ctypes.c_int32),
+        ("refit_rounds", ctypes.c_int32),
+    ]
+
+
+# acm_similarity_status, the doubles of a similarity (R row-major, t, s), the
+# per-set LDS staging budget and the flag bits (include/acm.h)
+SIMILARITY_OK, SIMILARITY_TOO_FEW_POINTS, SIMILARITY_NO_MODEL = 0, 1, 2
+SIMILARITY_DOUBLES = 13
+SIMILARITY_STAGE_POINTS = 1024
+SIMILARITY_RIGID = 1
+
+
 class CalibrateConfig(ctypes.Structure):
     """acm_calibrate_config (include/acm.h)."""
     _fields_ = [
@@ -312,6 +332,10 @@ EXPORTED_SYMBOLS = (
     "acm_homography_batch_default_config",
     "acm_homography_batch_workspace_size",
     "acm_homography_batch",
+    "acm_similarity_3pt",
+    "acm_similarity_batch_default_config",
+    "acm_similarity_batch_workspace_size",
+    "acm_similarity_batch",
     "acm_calibrate_default_config",
     "acm_calibrate_workspace_size",
     "acm_calibrate",
@@ -544,6 +568,18 @@ def load():
     L.acm_homography_batch.argtypes = [cam_p, sz, vp, sz, vp, vp, hg_p, vp, vp, vp, vp, vp, vp, vp,
                                        vp, vp, vp, vp, sz, vp]
     L.acm_homography_batch.restype = i
+    # n, points_a, points_b, flags, similarity, count, stream
+    L.acm_similarity_3pt.argtypes = [sz, vp, vp, ctypes.c_int32, vp, vp, vp]
+    L.acm_similarity_3pt.restype = i
+    sm_p = ctypes.POINTER(SimilarityConfig)
+    L.acm_similarity_batch_default_config.argtypes = [sm_p]
+    L.acm_similarity_batch_default_config.restype = None
+    L.acm_similarity_batch_workspace_size.argtypes = [sz, sz]
+    L.acm_similarity_batch_workspace_size.restype = sz
+    # n_sets, set_offsets, n_points, points_a, points_b, cfg, similarity, status, n_inliers,
+    # rms, mask, n_usable, workspace, workspace_bytes, stream
+    L.acm_similarity_batch.argtypes = [sz, vp, sz, vp, vp, sm_p, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    L.acm_similarity_batch.restype = i
     cal_p =ctypes.POINTER(CalibrateConfig)
     L.acm_calibrate_default_config.argtypes = [cal_p]
     L.acm_calibrate_default_config.restype = None

@@ -811,6 +811,159 @@ def estimate_homographies(model: CameraModel, pair_offsets, uv_a, uv_b,
                             n_usable)
 
 
+# ------------------------------------------------- 3-D similarity alignment
+def similarity_3pt(points_a, points_b, rigid: bool = False):
+    """The 3-point similarity solver (acm_similarity_3pt), batched: points_a,
+    points_b (N, 3, 3), three corresponding 3-D points in frame A and in frame
+    B.  Returns (similarity (N, 13) f64 -- b = s R a + t: R row-major, t, s --,
+    count (N,) u8) on the device; NaN and 0 where the triple is void
+    (collinear, coincident, not finite).  rigid: s fixed to 1."""
+    L = _lib.load()
+    pa = _as_device_f64(torch.as_tensor(points_a).reshape(-1, 3), 3)
+    pb = _as_device_f64(torch.as_tensor(points_b).reshape(-1, 3), 3)
+    if pa.shape[0] % 3 or pa.shape[0] != pb.shape[0]:
+        raise ValueError("points_a and points_b must both be (N, 3, 3)")
+    n = pa.shape[0] // 3
+    sim = torch.empty((n, _lib.SIMILARITY_DOUBLES), dtype=torch.float64, device="cuda")
+    count = torch.empty((n,), dtype=torch.uint8, device="cuda")
+    _lib.check(L.acm_similarity_3pt(n, pa.data_ptr() if n else None, pb.data_ptr() if n else None,
+                                    _lib.SIMILARITY_RIGID if rigid else 0,
+                                    sim.data_ptr() if n else None, count.data_ptr() if n else None,
+                                    _stream_handle()))
+    return sim, count
+
+
+@dataclass
+class SimilarityConfig:
+    """acm_similarity_config; the defaults are
+    acm_similarity_batch_default_config's.  The inlier distance is
+    estimate_similarities' own argument: it has no default."""
+    n_hypotheses: int = 256
+    seed: int = 1
+    min_inliers: int = 3
+    refit_rounds: int = 3
+    rigid: bool = False
+
+
+@dataclass
+class SimilarityResult:
+    """Device tensors, K sets: similarity (K, 13) f64 (b = s R a + t: R
+    row-major, t, s; NaN where status is not SIMILARITY_OK), status (K,) u8
+    (_lib.SIMILARITY_OK / SIMILARITY_TOO_FEW_POINTS / SIMILARITY_NO_MODEL),
+    n_inliers (K,) i32, rms (K,) f64 (over the inliers, in B's units),
+    n_usable (K,) i32, inlier_mask (M,) u8, one byte per correspondence."""
+    similarity: torch.Tensor
+    status: torch.Tensor
+    n_inliers: torch.Tensor
+    rms: torch.Tensor
+    n_usable: torch.Tensor
+    inlier_mask: torch.Tensor
+
+
+def estimate_similarities(set_offsets, points_a, points_b, inlier_distance: float,
+                          config: Optional[SimilarityConfig] = None) -> SimilarityResult:
+    """Every correspondence set's similarity b ~ s R a + t between two 3-D
+    frames (acm_similarity_batch): the 3-point absolute-orientation solver
+    inside RANSAC with a least-squares refit over the inliers, one workgroup
+    per set, all sets in one launch.  set_offsets (K + 1,) int64: set k owns
+    the rows set_offsets[k] .. set_offsets[k + 1] - 1 of points_a, points_b (M,
+    3).  inlier_distance: the largest |b - (s R a + t)| of an inlier, in frame
+    B's units."""
+    L = _lib.load()
+    offs = torch.as_tensor(set_offsets).to(device="cuda", dtype=torch.int64).contiguous()
+    pa = _as_device_f64(points_a, 3)
+    pb = _as_device_f64(points_b, 3)
+    k, m = offs.shape[0] - 1, pa.shape[0]
+    if k < 0 or pb.shape[0] != m:
+        raise ValueError("set_offsets needs K + 1 entries; points_a and points_b one row per correspondence")
+    c = config or SimilarityConfig()
+    cfg = _lib.SimilarityConfig()
+    L.acm_similarity_batch_default_config(ctypes.byref(cfg))
+    cfg.n_hypotheses = c.n_hypotheses
+    cfg.flags = _lib.SIMILARITY_RIGID if c.rigid else 0
+    cfg.seed = c.seed
+    cfg.inlier_distance = inlier_distance
+    cfg.min_inliers = c.min_inliers
+    cfg.refit_rounds = c.refit_rounds
+    sim = torch.empty((k, _lib.SIMILARITY_DOUBLES), dtype=torch.float64, device="cuda")
+    status = torch.empty((k,), dtype=torch.uint8, device="cuda")
+    n_inliers = torch.empty((k,), dtype=torch.int32, device="cuda")
+    rms = torch.empty((k,), dtype=torch.float64, device="cuda")
+    n_usable = torch.empty((k,), dtype=torch.int32, device="cuda")
+    mask = torch.zeros((m,), dtype=torch.uint8, device="cuda")  # entries no set owns stay 0
+    ws_bytes = L.acm_similarity_batch_workspace_size(k, m)
+    ws = torch.empty(((ws_bytes + 7) // 8,), dtype=torch.float64, device="cuda")
+    per_set = [x.data_ptr() if k else None for x in (sim, status, n_inliers, rms)]
+    _lib.check(L.acm_similarity_batch(
+        k, offs.data_ptr(), m, pa.data_ptr() if m else None, pb.data_ptr() if m else None,
+        ctypes.byref(cfg), *per_set, mask.data_ptr() if m else None,
+        n_usable.data_ptr() if k else None, ws.data_ptr(), ws_bytes, _stream_handle()))
+    return SimilarityResult(sim, status, n_inliers, rms, n_usable, mask)
+
+
+def _similarity_parts(similarity):
+    """(R (..., 3, 3), t (..., 3), s (...,)) of (..., 13) on the device."""
+    sim = torch.as_tensor(similarity).to(device="cuda", dtype=torch.float64)
+    if sim.shape[-1] != _lib.SIMILARITY_DOUBLES:
+        raise ValueError("a similarity has 13 entries: R row-major, t, s")
+    return sim[..., :9].reshape(*sim.shape[:-1], 3, 3), sim[..., 9:12], sim[..., 12]
+
+
+def _similarity_pack(R, t, s):
+    return torch.cat([R.reshape(*R.shape[:-2], 9), t, s.unsqueeze(-1)], dim=-1).contiguous()
+
+
+def apply_similarity(similarity, points, set_index=None):
+    """s R X + t on the device.  similarity (13,) or (K, 13); points (N, 3);
+    set_index (N,) integers: the row of `similarity` each point takes (None:
+    the one similarity given).  Returns (N, 3) f64."""
+    R, t, s = _similarity_parts(similarity)
+    X = _as_device_f64(points, 3)
+    if set_index is None:
+        if R.dim() == 3 and R.shape[0] != 1:
+            raise ValueError("several similarities need set_index")
+        R, t, s = R.reshape(1, 3, 3), t.reshape(1, 3), s.reshape(1)
+    else:
+        idx = torch.as_tensor(set_index).to(device="cuda", dtype=torch.int64).reshape(-1)
+        if idx.shape[0] != X.shape[0]:
+            raise ValueError("set_index needs one entry per point")
+        R, t, s = R.reshape(-1, 3, 3)[idx], t.reshape(-1, 3)[idx], s.reshape(-1)[idx]
+    return s.unsqueeze(-1) * torch.matmul(R, X.unsqueeze(-1)).squeeze(-1) + t
+
+
+def similarity_transform_poses(similarity, poses):
+    """View poses [R_c | t_c] given in frame A carried into frame B by the
+    similarity X_B = s R X_A + t (13,): [R_c R^T | s t_c - R_c R^T t], (V, 12).
+    From p_c = R_c X_A + t_c and X_A = R^T (X_B - t) / s: s p_c = R_c R^T X_B -
+    R_c R^T t + s t_c, so camera coordinates then come in B's unit."""
+    R, t, s = _similarity_parts(similarity)
+    if R.dim() != 2:
+        raise ValueError("similarity_transform_poses takes one similarity (13,)")
+    P = _poses_tensor(poses)
+    Rc, tc = P[:, :9].reshape(-1, 3, 3), P[:, 9:]
+    Rn = torch.matmul(Rc, R.t())
+    tn = s * tc - torch.matmul(Rn, t)
+    return torch.cat([Rn.reshape(-1, 9), tn], dim=1).contiguous()
+
+
+def similarity_compose(second, first):
+    """The similarity that applies `first`, then `second` ((..., 13) each,
+    broadcast): R = R2 R1, t = s2 R2 t1 + t2, s = s2 s1."""
+    R2, t2, s2 = _similarity_parts(second)
+    R1, t1, s1 = _similarity_parts(first)
+    R = torch.matmul(R2, R1)
+    t = s2.unsqueeze(-1) * torch.matmul(R2, t1.unsqueeze(-1)).squeeze(-1) + t2
+    return _similarity_pack(R, t, s2 * s1)
+
+
+def similarity_inverse(similarity):
+    """a = R^T (b - t) / s as a similarity: (R^T, -R^T t / s, 1 / s)."""
+    R, t, s = _similarity_parts(similarity)
+    Rt = R.transpose(-1, -2)
+    ti = -torch.matmul(Rt, t.unsqueeze(-1)).squeeze(-1) / s.unsqueeze(-1)
+    return _similarity_pack(Rt, ti, 1.0 / s)
+
+
 # ------------------------------------------------------ multi-view calibration
 @dataclass
 class CalibrationConfig:

@@ -37,6 +37,7 @@
 #include "p3p.hpp"
 #include "essential.hpp"
 #include "homography.hpp"
+#include "similarity.hpp"
 
 namespace acm {
 
@@ -3282,6 +3283,302 @@ __global__ __launch_bounds__(kBlock) void k_homography(CamArg cam, HomArgs a) {
         homography_pair<true>(a, pair, ob, cnt, usable, s_rec, (size_t)kHomStage, sh, hs);
     else
         homography_pair<false>(a, pair, ob, cnt, usable, wrec, wstride, sh, hs);
+}
+
+// ------------------------------------------------- 3-D similarity alignment
+// acm_similarity_3pt: one lane per problem, similarity.hpp's solver
+// (registers only).
+__global__ __launch_bounds__(kBlock) void k_similarity_3pt(
+    size_t n, const double* __restrict__ pa, const double* __restrict__ pb, int rigid,
+    double* __restrict__ sim, uint8_t* __restrict__ count) {
+    const size_t i = (size_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    double S[similarity::kDoubles];
+    const bool ok = similarity::similarity_3pt(pa + 9 * i, pb + 9 * i, rigid != 0, S);
+#pragma unroll
+    for (int q = 0; q < similarity::kDoubles; ++q) sim[similarity::kDoubles * i + q] = S[q];
+    count[i] = ok ? 1 : 0;
+}
+
+// acm_similarity_batch: RANSAC over the 3-point solver, one workgroup per
+// correspondence set, on the shared core (stage_records, ransac_select,
+// write_inlier_mask).  A record is the correspondence itself, (a, b): six
+// doubles.  The refit rounds run with the whole workgroup on one model.
+constexpr int kSimStage = ACM_SIMILARITY_STAGE_POINTS;  // per set; 48 B each
+
+struct SimArgs {
+    size_t n_points;
+    const int64_t* offs;
+    const double* pa;
+    const double* pb;
+    double* sim;
+    uint8_t* status;
+    uint32_t* n_inliers;
+    double* rms;
+    uint8_t* mask;
+    uint32_t* n_usable;
+    double* ws;  // six planes of n_points doubles
+    int H, min_inliers, refit_rounds, rigid;
+    unsigned long long seed;
+    double d2;  // inlier_distance^2
+};
+
+// what the workgroup shares through LDS beside RansacShared: the waves'
+// partial sums of a reduction and the current model
+struct SimShared {
+    double part[kBlock / 64][similarity::kSums];
+    double model[similarity::kDoubles];
+};
+
+// ransac_fail's sibling for a set without a similarity
+__device__ __forceinline__ void sim_fail(const SimArgs& a, size_t set, long long ob, long long cnt,
+                                         uint8_t st, uint32_t n) {
+    const int tid = threadIdx.x;
+    const double qnan = __builtin_nan("");
+    if (tid < similarity::kDoubles) a.sim[similarity::kDoubles * set + tid] = qnan;
+    if (tid == 0) {
+        a.status[set] = st;
+        a.n_inliers[set] = n;
+        if (a.rms) a.rms[set] = qnan;
+    }
+    if (a.mask)
+        for (long long j = tid; j < cnt; j += kBlock) a.mask[ob + j] = 0;
+}
+
+// The workgroup's sums of v[0 .. N - 1], N <= kSums: the fixed butterfly
+// within a wave, then the four waves in order, so the bits do not depend on
+// scheduling; every lane returns the same sums.  Ends with a barrier after
+// the last read of ss.part.
+template <int N>
+__device__ __forceinline__ void sim_reduce(double (&v)[N], SimShared& ss) {
+    static_assert(N <= similarity::kSums, "SimShared::part is too short");
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+#pragma unroll 1
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int q = 0; q < N; ++q) {
+            const double o = __shfl_down(v[q], off, 64);
+            if (lane < off) v[q] += o;
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < N; ++q) ss.part[wid][q] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < N; ++q) {
+        double s = ss.part[0][q];
+#pragma unroll
+        for (int w = 1; w < kBlock / 64; ++w) s += ss.part[w][q];
+        v[q] = s;
+    }
+    __syncthreads();
+}
+
+// record j is usable and within the inlier distance of the model S; e = e . e
+__device__ __forceinline__ bool sim_inlier(const double (&S)[similarity::kDoubles],
+                                           const double* __restrict__ rec, size_t stride,
+                                           long long j, double d2, double& e) {
+    const double ax = rec[j];
+    if (!__builtin_isfinite(ax)) return false;
+    e = similarity::residual2(S, ax, rec[stride + j], rec[2 * stride + j], rec[3 * stride + j],
+                              rec[4 * stride + j], rec[5 * stride + j]);
+    return e <= d2;
+}
+
+// (count, score) of the model S over all usable records, the lanes striding
+// over the records
+__device__ __forceinline__ void sim_score(const double (&S)[similarity::kDoubles],
+                                          const double* __restrict__ rec, size_t stride,
+                                          long long cnt, double d2, SimShared& ss, int& count,
+                                          double& score) {
+    double v[2] = {0.0, 0.0};  // the count is exact in a double
+    for (long long j = threadIdx.x; j < cnt; j += kBlock) {
+        double e;
+        if (sim_inlier(S, rec, stride, j, d2, e)) {
+            v[0] += 1.0;
+            v[1] += e;
+        }
+    }
+    sim_reduce(v, ss);
+    count = (int)v[0];
+    score = v[1];
+}
+
+// One refit round on the model S, in two passes over its inliers: the
+// centroids, then the sums centred on them (a one-pass raw-moment form
+// cancels for sets far from the origin).  false (workgroup-uniform): void.
+__device__ __forceinline__ bool sim_refit(const double (&S)[similarity::kDoubles],
+                                          const double* __restrict__ rec, size_t stride,
+                                          long long cnt, double d2, bool rigid, SimShared& ss,
+                                          double (&Q)[similarity::kDoubles]) {
+    const int tid = threadIdx.x;
+    double m[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // sum a, sum b, n
+#pragma unroll 1
+    for (long long j = tid; j < cnt; j += kBlock) {
+        double e;
+        if (!sim_inlier(S, rec, stride, j, d2, e)) continue;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) m[k] += rec[k * stride + j];
+        m[6] += 1.0;
+    }
+    sim_reduce(m, ss);
+    const double am[3] = {m[0] / m[6], m[1] / m[6], m[2] / m[6]};
+    const double bm[3] = {m[3] / m[6], m[4] / m[6], m[5] / m[6]};
+    double c[similarity::kSums];
+#pragma unroll
+    for (int q = 0; q < similarity::kSums; ++q) c[q] = 0.0;
+#pragma unroll 1
+    for (long long j = tid; j < cnt; j += kBlock) {
+        double e;
+        if (!sim_inlier(S, rec, stride, j, d2, e)) continue;
+        similarity::add_centred(c, am, bm, rec[j], rec[stride + j], rec[2 * stride + j],
+                                rec[3 * stride + j], rec[4 * stride + j], rec[5 * stride + j]);
+    }
+    sim_reduce(c, ss);
+    // every lane holds the same sums and runs the same fit
+    return similarity::fit((long long)m[6], am, bm, c, rigid, Q);
+}
+
+// One set's RANSAC, refit and outputs.  STAGED is not read in the body: it
+// only gives the LDS call (stride = kSimStage, a constant after inlining) a
+// copy of its own beside the workspace call, as homography_pair does.
+//
+// A hypothesis' score is added in record order within its lane; a refit's
+// score (sim_score) is added by sim_reduce's tree.  At an equal count
+// ransac::better therefore compares two summation orders: a refit that
+// leaves the inlier set and the model unchanged to rounding is accepted or
+// not on the last bits of the two sums.  Either way the outcome is a fixed
+// function of the set and the config (the same bits on every run), and the
+// model kept has the same count and the same score to rounding.
+template <bool STAGED>
+__device__ __forceinline__ void similarity_set(const SimArgs& a, size_t set, long long ob,
+                                               long long cnt, unsigned usable,
+                                               const double* __restrict__ rec, size_t stride,
+                                               RansacShared& sh, SimShared& ss) {
+    constexpr int kN = similarity::kDoubles;
+    const double qnan = __builtin_nan("");
+    const int tid = threadIdx.x;
+    const bool rigid = a.rigid != 0;
+    if (usable < 3u) return sim_fail(a, set, ob, cnt, ACM_SIMILARITY_TOO_FEW_POINTS, 0u);
+    // the lane's best: count (-1: no model), score, hypothesis, model
+    int bc = -1, bh = 0;
+    double bsum = 0.0, bm[kN];
+#pragma unroll
+    for (int k = 0; k < kN; ++k) bm[k] = qnan;
+#pragma unroll 1
+    for (int h = tid; h < a.H; h += kBlock) {
+        long long j0 = -1, j1 = -1, j2 = -1;
+        int got = 0;
+#pragma unroll 1
+        for (int d = 0; d < 6 && got < 3; ++d) {
+            const long long j = ransac::draw(a.seed, h, d, 6, cnt);
+            if (!__builtin_isfinite(rec[j]) || j == j0 || j == j1 || j == j2) continue;
+            j0 = got == 0 ? j : j0;
+            j1 = got == 1 ? j : j1;
+            j2 = got == 2 ? j : j2;
+            ++got;
+        }
+        if (got < 3) continue;
+        const double a0[3] = {rec[j0], rec[stride + j0], rec[2 * stride + j0]};
+        const double a1[3] = {rec[j1], rec[stride + j1], rec[2 * stride + j1]};
+        const double a2[3] = {rec[j2], rec[stride + j2], rec[2 * stride + j2]};
+        const double b0[3] = {rec[3 * stride + j0], rec[4 * stride + j0], rec[5 * stride + j0]};
+        const double b1[3] = {rec[3 * stride + j1], rec[4 * stride + j1], rec[5 * stride + j1]};
+        const double b2[3] = {rec[3 * stride + j2], rec[4 * stride + j2], rec[5 * stride + j2]};
+        double S[kN];
+        if (!similarity::solve3(a0, a1, a2, b0, b1, b2, rigid, S)) continue;
+        int c = 0;
+        double sum = 0.0;
+        for (long long j = 0; j < cnt; ++j) {
+            double e;
+            if (sim_inlier(S, rec, stride, j, a.d2, e)) {
+                ++c;
+                sum += e;
+            }
+        }
+        // h only grows in a lane: a tie keeps the earlier
+        if (c > bc || (c == bc && sum < bsum)) {
+            bc = c;
+            bsum = sum;
+            bh = h;
+#pragma unroll
+            for (int q = 0; q < kN; ++q) bm[q] = S[q];
+        }
+    }
+    const int winner = ransac_select<false>(sh, nullptr, ransac::Key{bc, bsum, bh, 0});
+    ransac::Key best{sh.count[0], sh.score[0], sh.h[0], 0};
+    if (best.count < a.min_inliers)  // also no model at all: count = -1
+        return sim_fail(a, set, ob, cnt, ACM_SIMILARITY_NO_MODEL,
+                        best.count < 0 ? 0u : (uint32_t)best.count);
+    if (tid == winner) {
+#pragma unroll
+        for (int q = 0; q < kN; ++q) ss.model[q] = bm[q];
+    }
+    __syncthreads();  // also: every lane has read sh.count[0], sh.score[0] and sh.h[0]
+    double S[kN];
+#pragma unroll
+    for (int q = 0; q < kN; ++q) S[q] = ss.model[q];
+    // the refit: every condition below is the same in all lanes
+#pragma unroll 1
+    for (int round = 0; round < a.refit_rounds; ++round) {
+        double Q[kN];
+        if (!sim_refit(S, rec, stride, cnt, a.d2, rigid, ss, Q)) break;
+        ransac::Key k{0, 0.0, best.h, 0};
+        sim_score(Q, rec, stride, cnt, a.d2, ss, k.count, k.score);
+        if (!ransac::better(k, best)) break;
+        best = k;
+#pragma unroll
+        for (int q = 0; q < kN; ++q) S[q] = Q[q];
+    }
+    double rms = qnan;
+    if (a.rms) {  // the final inliers' residuals, added by the fixed tree
+        int c;
+        double sum;
+        sim_score(S, rec, stride, cnt, a.d2, ss, c, sum);
+        rms = sqrt(sum / (double)c);
+    }
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 0; q < kN; ++q) a.sim[kN * set + q] = S[q];
+        a.status[set] = ACM_SIMILARITY_OK;
+        a.n_inliers[set] = (uint32_t)best.count;
+        if (a.rms) a.rms[set] = rms;
+    }
+    write_inlier_mask(a.mask, ob, cnt, rec, stride,
+                      [&](double ax, double ay, double az, double bx, double by, double bz) {
+                          return similarity::residual2(S, ax, ay, az, bx, by, bz) <= a.d2;
+                      });
+}
+
+__global__ __launch_bounds__(kBlock) void k_similarity(SimArgs a) {
+    __shared__ double s_rec[6 * kSimStage];  // planes a.x, a.y, a.z, b.x, b.y, b.z
+    __shared__ RansacShared sh;
+    __shared__ SimShared ss;
+    const size_t set = blockIdx.x;
+    long long ob, cnt;
+    clamped_range(a.offs, set, a.n_points, ob, cnt);
+    const bool staged = cnt <= (long long)kSimStage;  // workgroup-uniform
+    // the records: j < cnt <= n_points - ob, so a workspace plane is never overrun
+    double* wrec = a.ws + ob;
+    const size_t wstride = a.n_points;
+    const unsigned usable = stage_records<kSimStage>(
+        cnt, staged, s_rec, wrec, wstride, sh.usable, [&](long long j, double(&r)[6]) {
+            bool ok = true;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                r[k] = a.pa[3 * (ob + j) + k];
+                r[3 + k] = a.pb[3 * (ob + j) + k];
+                ok = ok && __builtin_isfinite(r[k]) && __builtin_isfinite(r[3 + k]);
+            }
+            return ok;
+        });
+    if (threadIdx.x == 0 && a.n_usable) a.n_usable[set] = usable;
+    if (staged)
+        similarity_set<true>(a, set, ob, cnt, usable, s_rec, (size_t)kSimStage, sh, ss);
+    else
+        similarity_set<false>(a, set, ob, cnt, usable, wrec, wstride, sh, ss);
 }
 
 // ------------------------------------------------------------ calibration
@@ -7873,6 +8170,79 @@ ACM_API int acm_homography_batch(const acm_camera* cam, size_t n_pairs,
                            prep(*cam, false, true), a);
         return check_launch("acm_homography_batch");
     });
+}
+
+ACM_API int acm_similarity_3pt(size_t n, const double* points_a, const double* points_b,
+                               int32_t flags, double* similarity, uint8_t* count, void* stream) {
+    if (flags & ~ACM_SIMILARITY_RIGID) return fail(ACM_ERR_INVALID_ARGUMENT, "unknown flags");
+    if (n == 0) return ACM_SUCCESS;
+    if (!points_a || !points_b || !similarity || !count)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (n > (size_t)0x7fffffff * kBlock)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many problems for one launch");
+    const unsigned nb = (unsigned)((n + kBlock - 1) / kBlock);
+    hipLaunchKernelGGL(k_similarity_3pt, dim3(nb), dim3(kBlock), 0, (hipStream_t)stream, n, points_a,
+                       points_b, (int)(flags & ACM_SIMILARITY_RIGID), similarity, count);
+    return check_launch("acm_similarity_3pt");
+}
+
+ACM_API void acm_similarity_batch_default_config(acm_similarity_config* cfg) {
+    if (!cfg) return;
+    cfg->n_hypotheses = 256;
+    cfg->flags = 0;
+    cfg->seed = 1;
+    cfg->inlier_distance = 0.0;  // in B's units: the caller sets it
+    cfg->min_inliers = 3;
+    cfg->refit_rounds = 3;
+}
+
+// 64 reserved bytes, then the records of the sets too long for LDS: six
+// planes of n_points doubles (a set uses its own range of each plane)
+ACM_API size_t acm_similarity_batch_workspace_size(size_t, size_t n_points) {
+    return 64 + 48 * n_points;
+}
+
+ACM_API int acm_similarity_batch(size_t n_sets, const int64_t* set_offsets, size_t n_points,
+                                 const double* points_a, const double* points_b,
+                                 const acm_similarity_config* cfg, double* similarity,
+                                 uint8_t* status, uint32_t* n_inliers, double* rms,
+                                 uint8_t* inlier_mask, uint32_t* n_usable, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    if (!cfg) return fail(ACM_ERR_INVALID_ARGUMENT, "config is NULL");
+    if (cfg->n_hypotheses < 1 || cfg->n_hypotheses > 65536 || (cfg->flags & ~ACM_SIMILARITY_RIGID) ||
+        !(std::isfinite(cfg->inlier_distance) && cfg->inlier_distance > 0.0) ||
+        cfg->min_inliers < 3 || cfg->refit_rounds < 0 || cfg->refit_rounds > 8)
+        return fail(ACM_ERR_INVALID_ARGUMENT,
+                    "n_hypotheses outside 1 .. 65536, unknown flags, inlier_distance not finite and "
+                    "> 0, min_inliers < 3 or refit_rounds outside 0 .. 8");
+    if (n_sets == 0) return ACM_SUCCESS;
+    if (!similarity || !set_offsets || !status || !n_inliers ||
+        (n_points && (!points_a || !points_b)))
+        return fail(ACM_ERR_INVALID_ARGUMENT, "NULL buffer");
+    if (!workspace || workspace_bytes < acm_similarity_batch_workspace_size(n_sets, n_points))
+        return fail(ACM_ERR_WORKSPACE_TOO_SMALL, "similarity workspace too small");
+    if (n_sets > (size_t)0x7fffffff)
+        return fail(ACM_ERR_INVALID_ARGUMENT, "too many sets for one launch");
+    SimArgs a;
+    a.n_points = n_points;
+    a.offs = set_offsets;
+    a.pa = points_a;
+    a.pb = points_b;
+    a.sim = similarity;
+    a.status = status;
+    a.n_inliers = n_inliers;
+    a.rms = rms;
+    a.mask = inlier_mask;
+    a.n_usable = n_usable;
+    a.ws = reinterpret_cast<double*>(static_cast<char*>(workspace) + 64);
+    a.H = cfg->n_hypotheses;
+    a.min_inliers = cfg->min_inliers;
+    a.refit_rounds = cfg->refit_rounds;
+    a.rigid = cfg->flags & ACM_SIMILARITY_RIGID;
+    a.seed = cfg->seed;
+    a.d2 = cfg->inlier_distance * cfg->inlier_distance;
+    hipLaunchKernelGGL(k_similarity, dim3((unsigned)n_sets), dim3(kBlock), 0, (hipStream_t)stream, a);
+    return check_launch("acm_similarity_batch");
 }
 
 ACM_API void acm_calibrate_default_config(acm_calibrate_config* cfg) {

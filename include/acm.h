@@ -1116,6 +1116,133 @@ ACM_API int acm_homography_batch(const acm_camera *cam, size_t n_pairs,
                                  double *translation, uint8_t *inlier_mask, uint32_t *n_usable,
                                  void *workspace, size_t workspace_bytes, void *stream);
 
+/* 3-D similarity alignment (absolute orientation, Horn, Umeyama, Sim(3)): the
+ * least-squares b ~ s R a + t between two 3-D point sets, the 3-point solver
+ * and RANSAC over it.  It relates two frames that hold the same points: two
+ * two-view reconstructions (each in camera A's frame of its pair, in units of
+ * its baseline), or a reconstruction and a surveyed frame.  No camera enters
+ * these calls: they work on 3-D points alone.
+ *
+ * A similarity is ACM_SIMILARITY_DOUBLES = 13 f64: R row-major (9), t (3), s.
+ *
+ * acm_similarity_3pt: n independent problems of three correspondences, one
+ * lane each.  points_a, points_b: 9 n f64, problem i holds its three points
+ * a_0, a_1, a_2 and b_0, b_1, b_2.  flags: 0, or ACM_SIMILARITY_RIGID for s
+ * fixed to 1.  Outputs per problem: similarity (13 f64) and count, one byte, 1
+ * or 0.
+ *
+ * The route, f64 throughout, serves any number n >= 3 of correspondences (the
+ * refit below reuses it).  The centroids am, bm; the sums centred on them, M =
+ * sum (b - bm)(a - am)^T and Saa = sum |a - am|^2, in index order; Horn's
+ * symmetric 4 x 4 matrix N of M (Horn, Closed-form solution of absolute
+ * orientation using unit quaternions, 1987), whose largest eigenvalue's
+ * eigenvector is the unit quaternion q of R.  The eigenpairs come from a
+ * cyclic Jacobi of six sweeps over the six off-diagonal entries, no early
+ * exit.  q is signed so that q_0 >= 0 (at q_0 = 0 the first non-zero component
+ * is positive) and gives a proper rotation: det R = +1 also for a planar or
+ * mirrored set.  s = sum (b - bm) . R (a - am) / Saa = sum_rc R_rc M_rc / Saa
+ * (1 with ACM_SIMILARITY_RIGID), t = bm - s R am.  The three points enter
+ * through sums only, so the result does not hinge on their order beyond
+ * rounding.
+ *
+ * Void -- every output NaN, count 0: an input or output that is not finite;
+ * Saa <= 0 (all a coincide); s <= 0; or, with N's eigenvalues lambda_1 >=
+ * lambda_2, not (lambda_1 > 0 and lambda_1 - lambda_2 > 1e-9 lambda_1).  The
+ * last covers a collinear configuration (two coincident points included),
+ * which leaves the rotation about its line free: its relative gap is at the
+ * rounding level, a triangle's well above (>= 2e-4 when sin^2 of the angle at
+ * its first vertex is >= 0.01).  n = 0 is valid.  NULL buffers with n > 0 or
+ * unknown flag bits: ACM_ERR_INVALID_ARGUMENT.  No workspace, stream-ordered,
+ * reentrant.
+ *
+ * acm_similarity_batch: RANSAC over that solver, one 256-lane workgroup per
+ * correspondence set, all sets in one launch.  The correspondences are CSR by
+ * set: set k owns the rows set_offsets[k] .. set_offsets[k + 1] - 1 of
+ * points_a and points_b (n_points x 3 f64 each); the offsets are clamped into
+ * [0, n_points] and a decreasing pair gives an empty set, so nothing is read
+ * out of bounds.  A correspondence is usable iff its six values are finite;
+ * n_usable (nullable) counts them.  The records, (a, b) of 48 B, stay in LDS
+ * for a set of at most ACM_SIMILARITY_STAGE_POINTS correspondences and in the
+ * set's own range of six workspace planes beyond.
+ *
+ * Hypothesis h = 0 .. n_hypotheses - 1 (lanes stride over h) draws local
+ * indices with the splitmix64 of acm_pose_estimate_batch and ctr = 6 h + d + 1
+ * for the draws d = 0 .. 5.  The first three draws that are usable and
+ * pairwise distinct form the sample; otherwise the hypothesis is void, as it
+ * is when the solver above is.  The model is scored over all usable
+ * correspondences of the set in order: with e = b - (s R a + t) one is an
+ * inlier iff e . e <= inlier_distance^2.  The key of a hypothesis is (inlier
+ * count descending, sum over the inliers of e . e ascending, h ascending), a
+ * total order.
+ *
+ * Refit: up to refit_rounds times the route above runs over the current
+ * model's inliers in two passes -- the centroids, then the centred sums (a
+ * one-pass raw-moment form would cancel for sets far from the origin) -- lane
+ * l taking the correspondences l, l + 256, ..., the sums added by the fixed
+ * butterfly within a wave, then the four waves in order.  The result is
+ * scored; it replaces the model iff its key is strictly better, otherwise (or
+ * when the fit is void) the loop ends.  A hypothesis' score is added in record
+ * order, a refit's score by that fixed tree: at an equal count the comparison
+ * is between two summation orders of e . e, so a refit that changes neither
+ * the inlier set nor the model beyond rounding is taken or not on the last
+ * bits of the two sums -- deterministically, and with the same count and the
+ * same score to rounding either way.
+ *
+ * Outputs per set: similarity (13 f64, required), status
+ * (acm_similarity_status, required), n_inliers (required) and, each nullable,
+ * rms (sqrt(sum e . e / n_inliers) over the final inliers, added by the same
+ * fixed tree), inlier_mask (one byte per correspondence) and n_usable.  Fewer
+ * than 3 usable correspondences: ACM_SIMILARITY_TOO_FEW_POINTS.  No hypothesis
+ * with a model, or a best count below min_inliers (no refit then):
+ * ACM_SIMILARITY_NO_MODEL with n_inliers = the best count (0 without a model).
+ * In both cases the similarity and rms are NaN and the set's mask 0.
+ *
+ * A set's outputs depend only on its own list in order and the config, and
+ * repeated calls return the same bits.  Errors (ACM_ERR_INVALID_ARGUMENT,
+ * checked even when there is nothing to do): cfg NULL, n_hypotheses outside 1
+ * .. 65536, flags other than 0 or ACM_SIMILARITY_RIGID, inlier_distance not
+ * finite or <= 0 (the default config holds 0: the caller sets it, in B's
+ * units), min_inliers < 3, refit_rounds outside 0 .. 8; with n_sets > 0 a NULL
+ * required buffer; a workspace that is NULL or smaller than
+ * acm_similarity_batch_workspace_size: ACM_ERR_WORKSPACE_TOO_SMALL.  n_sets =
+ * 0 is valid and touches nothing.  Stream-ordered, no allocation, no host
+ * synchronisation, reentrant (two calls in flight need two workspaces).
+ *
+ * Out of scope: weights per correspondence; anisotropic scale; a robust loss
+ * in place of the inlier threshold. */
+#define ACM_SIMILARITY_DOUBLES 13
+/* correspondences of one set whose records stay in LDS (48 B each); a longer
+ * set keeps them in the workspace */
+#define ACM_SIMILARITY_STAGE_POINTS 1024
+#define ACM_SIMILARITY_RIGID 1 /* flags bit 0: s fixed to 1 */
+
+ACM_API int acm_similarity_3pt(size_t n, const double *points_a, const double *points_b,
+                               int32_t flags, double *similarity, uint8_t *count, void *stream);
+
+typedef enum acm_similarity_status {
+    ACM_SIMILARITY_OK = 0,
+    ACM_SIMILARITY_TOO_FEW_POINTS = 1, /* fewer than 3 usable correspondences */
+    ACM_SIMILARITY_NO_MODEL = 2        /* no finite model, or fewer than min_inliers inliers */
+} acm_similarity_status;
+
+typedef struct acm_similarity_config {
+    int32_t n_hypotheses;   /* default 256; 1 .. 65536 */
+    int32_t flags;          /* 0 or ACM_SIMILARITY_RIGID */
+    uint64_t seed;          /* default 1 */
+    double inlier_distance; /* in B's units; finite, > 0; the default config holds 0 */
+    int32_t min_inliers;    /* default 3; >= 3 */
+    int32_t refit_rounds;   /* default 3; 0 .. 8 */
+} acm_similarity_config;
+
+ACM_API void acm_similarity_batch_default_config(acm_similarity_config *cfg);
+ACM_API size_t acm_similarity_batch_workspace_size(size_t n_sets, size_t n_points);
+ACM_API int acm_similarity_batch(size_t n_sets, const int64_t *set_offsets, size_t n_points,
+                                 const double *points_a, const double *points_b,
+                                 const acm_similarity_config *cfg, double *similarity,
+                                 uint8_t *status, uint32_t *n_inliers, double *rms,
+                                 uint8_t *inlier_mask, uint32_t *n_usable, void *workspace,
+                                 size_t workspace_bytes, void *stream);
+
 /* Multi-view calibration: the intrinsics and every view's pose in one
  * Levenberg-Marquardt.  K views of known world points, rough poses (device,
  * in/out) and rough intrinsics (cam, host, in/out); the unknowns are the P
