@@ -30,6 +30,10 @@ Families (sample parameters of samples/*.yaml unless noted):
                             (UCM, DS), also at |p| ~ 1e13
   UCM unproject             1 - r^2 = 1e-3 (_alpha_le_half_probes says why
                             DS and EUCM have no reachable threshold there)
+
+probes_f32() restates the projection families for acm_project_f32 (f32
+parameters, float thresholds, f32 steps), and emulate_status takes the
+precision to round to (53 by default; 24 is binary32, 170 stands for exact).
 """
 import mpmath
 import numpy as np
@@ -235,13 +239,15 @@ def pix(p, mx_target_sq, scale):
 
 
 # ----------------------------------------------------------- f64 emulation
-def _st_project(model, p, w, h, pt):
+def _st_project(model, p, w, h, pt, f32_thresholds=False):
     from mpmath import mpf, sqrt
     x, y, z = (mpf(float(c)) for c in pt)
     P = [mpf(float(c)) for c in p]
     fx, fy, cx, cy = P[:4]
     one, two = mpf(1), mpf(2)
-    pr = mpf("1e-3")
+    # the f32 kernel's thresholds are the f64 constants cast to float: EPS =
+    # 2^-52 and sqrt(EPS) = 2^-26 are unchanged, 1e-3 becomes float(1e-3)
+    pr = mpf(float(np.float32(1e-3))) if f32_thresholds else mpf("1e-3")
     if model in (0, 1):  # pinhole.rs:165-182, rad_tan.rs:302-348
         if z < mpf(EPS_SQRT):
             return 3
@@ -396,9 +402,161 @@ def _st_unproject(model, p, w, h, uv):
     raise ValueError(model)
 
 
-def emulate_status(model, p, w, h, kind, pt):
-    """The reference's status for one probe, in binary64 (mpmath, 53 bits)."""
-    with mpmath.workprec(53):
+def emulate_status(model, p, w, h, kind, pt, prec=53, f32_thresholds=False):
+    """The reference's status for one probe with every operation rounded to
+    `prec` bits (mpmath, round to nearest even, unbounded exponent): 53 is
+    binary64, 24 binary32 for values whose squares neither over- nor
+    underflow, 170 stands for exact.  f32_thresholds (projections only):
+    compare against float(1e-3) as acm_project_f32 does."""
+    with mpmath.workprec(prec):
         if kind == "project":
-            return _st_project(model, p, w, h, pt)
+            return _st_project(model, p, w, h, pt, f32_thresholds)
         return _st_unproject(model, p, w, h, pt)
+
+
+# ------------------------------------------------------------ f32 probes
+# The f64 families above step by f64 ulps: rounded to f32, all 17 probes of a
+# family are one value.  probes_f32 restates the projection families for
+# acm_project_f32: the camera parameters rounded to f32, the threshold the
+# kernel compares against (float(1e-3); 2^-52 and 2^-26 are f32 values), the
+# root found at those values, and the continuous parameter stepped over the
+# f32 neighbours -32 .. +32 of the root.
+F32_STEPS = 32
+
+
+def f32_steps(t, k=F32_STEPS):
+    """(2k + 1,) float64: the f32 nearest to t and its k neighbours on either
+    side, ascending (index k is the f32 nearest to t)."""
+    c = np.float32(float(t))
+    lo, hi = [c], [c]
+    for _ in range(k):
+        lo.append(np.nextafter(lo[-1], np.float32(-np.inf)))
+        hi.append(np.nextafter(hi[-1], np.float32(np.inf)))
+    return np.array(lo[:0:-1] + hi, dtype=np.float64)
+
+
+def _r32(v):
+    return float(np.float32(v))
+
+
+def _line(fixed, t):
+    """(len(t), 3): the coordinates of `fixed`, None standing for the stepped t."""
+    return np.stack([np.full(len(t), c) if c is not None else t for c in fixed], 1)
+
+
+def probes_f32():
+    """[(label, key, points (65, 3))]: one probe line per entry, projection
+    only, key a model id or camera_zoo name (its parameters are used rounded
+    to f32: f32_ref.params32).  Along a line the status changes at index
+    F32_STEPS (the root) and nowhere else, in exact arithmetic.
+
+    Families: UCM / DS / EUCM denom = float(1e-3) at three radii; UCM / DS
+    z = -w d (DS: -w2 d1) and EUCM z = denom (a - 1) / (2a - 1); KB z = 0
+    (denormal neighbours) and z = 2^-52; Pinhole / RadTan / FOV z = 2^-26;
+    Pinhole / RadTan u = 0, u = w and v = h; and the alpha <= 0.5 cameras'
+    denom = float(1e-3) and DS's z = -w2 d1 at alpha < 0.5 (at alpha = 0.5
+    w2 = 1 and the root is at -inf; UCM's condition is implied by its denom
+    there, _alpha_le_half_probes).
+    The f64 families at |p| ~ 1e13 are not restated: they sit where one f64
+    ulp of alpha d is 1e-3, which has no f32 counterpart inside the range
+    whose squares stay finite.  KB's axis test r < EPS shapes values only:
+    f32_ref.kb_axis_points."""
+    from camera_zoo import camera_of
+    mp = mpmath
+    thr = mp.mpf(_r32(1e-3))
+    out = []
+
+    def p32(key):
+        return [mp.mpf(_r32(c)) for c in camera_of(key)[1]]
+
+    def z_line(label, key, r, f, z_start):
+        r = _r32(r)
+        z0 = _root(lambda z: f(z, mp.mpf(r)), z_start)
+        out.append((label, key, _line((r, r, None), f32_steps(z0))))
+
+    def ucm_den(a):
+        return lambda z, r: a * mp.sqrt(2 * r * r + z * z) + (1 - a) * z - thr
+
+    def ds_den(a, xi):
+        def den(z, r):
+            d1 = mp.sqrt(2 * r * r + z * z)
+            g = xi * d1 + z
+            return a * mp.sqrt(2 * r * r + g * g) + (1 - a) * g - thr
+        return den
+
+    def eucm_den(a, b):
+        return lambda z, r: a * mp.sqrt(b * 2 * r * r + z * z) + (1 - a) * z - thr
+
+    # ---- alpha > 0.5: the sample cameras
+    a = p32(4)[4]
+    w = (1 - a) / a
+    for r in (1e-4, 3e-4, 6e-4):
+        z_line(f"ucm denom r={r}", 4, r, ucm_den(a), 1e-3)
+        z_line(f"ucm z=-wd r={r * 1e3}", 4, r * 1e3,
+               lambda z, r, w=w: z + w * mp.sqrt(2 * r * r + z * z), r)
+    a, xi = p32(3)[4:6]
+    w1 = (1 - a) / a
+    w2 = (w1 + xi) / mp.sqrt(2 * w1 * xi + xi * xi + 1)
+    for r in (1e-4, 4e-4):
+        z_line(f"ds denom r={r}", 3, r, ds_den(a, xi), 1e-3)
+    # (at r = 1e-4 and 4e-4 denom < 1e-3 hides this condition: r = 0.3 only;
+    # likewise EUCM's below at r = 1)
+    z_line("ds z=-w2d1 r=0.3", 3, 0.3, lambda z, r, w2=w2: z + w2 * mp.sqrt(2 * r * r + z * z),
+           -0.3)
+    a, b = p32(5)[4:6]
+    c = (a - 1) / (2 * a - 1)
+    for r in (1e-4, 5e-4):
+        z_line(f"eucm denom r={r}", 5, r, eucm_den(a, b), 1e-3)
+    z_line("eucm z=denom c r=1.0", 5, 1.0,
+           lambda z, r, a=a, b=b, c=c: z - (eucm_den(a, b)(z, r) + thr) * c, 0.1)
+    # ---- KB: z < 0 and z < EPS
+    x, y = _r32(0.3), _r32(-0.2)
+    out.append(("kb z=0", 2, _line((x, y, None), f32_steps(0.0))))
+    out.append(("kb z=EPS", 2, _line((x, y, None), f32_steps(EPS))))
+    # ---- Pinhole / RadTan / FOV: z < sqrt(EPS); Pinhole / RadTan image bounds
+    # (RadTan at x = y = 1e-4: at 0.1 its r^6 = 2 (x / z)^2 cubed overflows f32
+    # and the pixel is NaN, which no bounds test rejects)
+    for key, name, xy in ((0, "pinhole", 0.1), (1, "radtan", 1e-4), (6, "fov", 0.1)):
+        out.append((f"{name} z=sqrt(EPS)", key,
+                    _line((_r32(xy), _r32(xy), None), f32_steps(EPS_SQRT))))
+    import mp_models
+    for key, name in ((0, "pinhole"), (1, "radtan")):
+        model, _, (wd, ht) = camera_of(key)
+        P = p32(key)
+        for lab, axis, target in (("u=w", 0, wd), ("u=0", 0, 0), ("v=h", 1, ht)):
+            def f(t, axis=axis, target=target):
+                pt = [t, 0, 2] if axis == 0 else [0, t, 2]
+                return mp_models.project(model, P, pt)[axis] - target
+            t0 = _root(f, (target - float(P[2 + axis])) / float(P[axis]) * 2.0)
+            t = f32_steps(t0)
+            fixed = (None, 0.0, 2.0) if axis == 0 else (0.0, None, 2.0)
+            out.append((f"{name} {lab}", key, _line(fixed, t)))
+    # ---- alpha <= 0.5 (boundary_probes._alpha_le_half_probes says which
+    # conditions are reachable there)
+    for key in ("ucm_alpha_lt_half", "ucm_alpha_half"):
+        a = p32(key)[4]
+        # at alpha = 0.5 denom = (d + z) / 2 cancels for z < 0: at r = 0.3 (the
+        # f64 family's radius, root z = -45) the binary32 denom is noise over
+        # the whole line (W = 32) and nothing but "one of two statuses" could
+        # be asserted; at r = 0.005 W is a few steps
+        for r, z_start in ((1e-4, 1e-3), (6e-4, 1e-3),
+                           (0.3, -0.2) if a < 0.5 else (0.005, -0.0125)):
+            z_line(f"{key} denom r={r}", key, r, ucm_den(a), z_start)
+    for key in ("ds_alpha_lt_half", "ds_alpha_half"):
+        a, xi = p32(key)[4:6]
+        for r, z_start in ((1e-4, 1e-3), (4e-4, 1e-3), (0.005, -0.0125)):
+            if r == 0.005 and a < 0.5:
+                continue  # z = -w2 d1 fails first at a third radius there
+            z_line(f"{key} denom r={r}", key, r, ds_den(a, xi), z_start)
+    a, xi = p32("ds_alpha_lt_half")[4:6]
+    w1 = a / (1 - a)
+    w2 = (w1 + xi) / mp.sqrt(2 * w1 * xi + xi * xi + 1)
+    for r in (0.1, 0.4):
+        z_line(f"ds_alpha_lt_half z=-w2d1 r={r}", "ds_alpha_lt_half", r,
+               lambda z, r, w2=w2: z + w2 * mp.sqrt(2 * r * r + z * z), -r)
+    for key in ("eucm_alpha_lt_half", "eucm_alpha_half"):
+        a, b = p32(key)[4:6]
+        for r, z_start in ((1e-4, 1e-3), (5e-4, 1e-3),
+                           (0.3, -0.3) if a < 0.5 else (0.003, -0.009)):  # as UCM's
+            z_line(f"{key} denom r={r}", key, r, eucm_den(a, b), z_start)
+    return out

@@ -628,6 +628,19 @@ def test_f32_path_tracks_f64(golden_dir, model):
     u0 = g["uv"][keep][both]
     err = np.abs(uv.cpu().numpy()[both].astype(np.float64) - u0) / np.maximum(np.abs(u0), 1.0)
     assert np.nanmax(err) < 1e-4
+    # every Jacobian entry, against the oracle at the values the kernel saw
+    # (parameters and points rounded to f32): tests/f32_ref.py's bound for the
+    # model (these are not the rows its per-camera figures were measured on)
+    import f32_ref as F
+    xyz32 = F.points32(xyz)
+    _, st32, J0 = O.project(model, F.round32(params), w, h, xyz32, want_jac=True)
+    rows = both & (st32 == 0) & F.in_range(xyz32)
+    worst, (q, i, a) = F.jac_ratio(J.cpu().numpy(), J0, rows)
+    print(f"f32 golden rows model {model}: {int(rows.sum())} rows, worst J entry {worst:.3f} x "
+          f"2^-24 scale (parameter {q}), / bound {worst / F.K_J_MODEL[model]:.3f}")
+    assert int(rows.sum()) >= 240
+    assert worst <= F.K_J_MODEL[model], (worst, q, a, xyz32[i].tolist())
+    assert F.structural_exact(J.cpu().numpy(), st == 0)
 
 
 @pytest.mark.parametrize("model", [2, 3])
